@@ -3,12 +3,20 @@ import sys
 
 # xdist runs 4 workers on an 8-core box: cap intra-op threads per worker so
 # the model matrix doesn't thrash on oversubscribed OpenMP pools
+_omp_preset = os.environ.get('OMP_NUM_THREADS', '')
 os.environ.setdefault('OMP_NUM_THREADS', '2')
 
 import pytest
 import torch
 
-torch.set_num_threads(max(1, (os.cpu_count() or 8) // 4))
+# a quarter of the usable CPUs per worker, but never more than 4 threads (the
+# test models are tiny; on a big shared host cpu_count()//4 gave 4 workers x 64+
+# threads fighting over a small CPU share) nor more than OMP_NUM_THREADS allows
+_cpus = len(os.sched_getaffinity(0)) if hasattr(os, 'sched_getaffinity') else (os.cpu_count() or 8)
+_threads = min(_cpus // 4, 4)
+if _omp_preset.isdigit():
+    _threads = min(_threads, int(_omp_preset))
+torch.set_num_threads(max(1, _threads))
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 

@@ -1,4 +1,4 @@
-"""Import the reference timm (/root/reference) for behavior-parity testing.
+"""Import the reference timm from a local checkout for behavior-parity testing.
 
 The reference imports torchvision at package level; this environment has no
 torchvision, so minimal stubs are installed first.  Test-only helper — the
@@ -88,10 +88,10 @@ def _stub_torchvision():
     sys.modules['torchvision.datasets'] = datasets
 
 
-def load_reference():
-    """Returns the reference `timm` package (imported from /root/reference)."""
+def load_reference(ref_path):
+    """Returns the reference `timm` package, imported from the checkout at ref_path."""
     _stub_torchvision()
-    if '/root/reference' not in sys.path:
-        sys.path.insert(0, '/root/reference')
+    if ref_path not in sys.path:
+        sys.path.insert(0, ref_path)
     import timm  # noqa
     return timm
