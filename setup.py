@@ -24,6 +24,7 @@ sources = [
     os.path.join(CSRC, 'muon_ns.hip'),
     os.path.join(CSRC, 'ce_loss.hip'),
     os.path.join(CSRC, 'data_ops.hip'),
+    os.path.join(CSRC, 'rope.hip'),
 ]
 
 setup(

@@ -13,6 +13,7 @@ from .cond_conv2d import CondConv2d, get_condconv_initializer
 from .config import (
     is_exportable, is_no_jit, is_scriptable, set_exportable, set_layer_config, set_no_jit, set_scriptable,
     set_fused_attn, use_fused_attn, set_reentrant_ckpt, use_reentrant_ckpt,
+    set_fused_rope, use_fused_rope,
 )
 from .conv2d_same import Conv2dSame, Conv2dSameExport, conv2d_same
 from .conv_bn_act import ConvBnAct, ConvNormAct, ConvNormActAa

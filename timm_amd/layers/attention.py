@@ -11,7 +11,7 @@ import torch
 from torch import nn
 
 from .. import ops
-from .config import use_fused_attn
+from .config import use_fused_attn, use_fused_rope
 from .pos_embed_sincos import apply_rot_embed_cat
 
 
@@ -175,10 +175,13 @@ class AttentionRope(nn.Module):
         if rope is not None:
             npt = self.num_prefix_tokens
             half = self.rotate_half
-            q = torch.cat(
-                [q[:, :, :npt, :], apply_rot_embed_cat(q[:, :, npt:, :], rope, half=half)], dim=2).type_as(v)
-            k = torch.cat(
-                [k[:, :, :npt, :], apply_rot_embed_cat(k[:, :, npt:, :], rope, half=half)], dim=2).type_as(v)
+            if use_fused_rope():
+                q, k = ops.apply_rope_qk(q, k, rope, num_prefix_tokens=npt, half=half, out_dtype=v.dtype)
+            else:
+                q = torch.cat(
+                    [q[:, :, :npt, :], apply_rot_embed_cat(q[:, :, npt:, :], rope, half=half)], dim=2).type_as(v)
+                k = torch.cat(
+                    [k[:, :, :npt, :], apply_rot_embed_cat(k[:, :, npt:, :], rope, half=half)], dim=2).type_as(v)
 
         if self.fused_attn:
             x = ops.flash_attention(

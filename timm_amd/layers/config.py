@@ -13,6 +13,7 @@ from typing import Any, Optional
 __all__ = [
     'is_no_jit', 'set_no_jit', 'is_exportable', 'set_exportable', 'is_scriptable', 'set_scriptable',
     'set_layer_config', 'use_fused_attn', 'set_fused_attn', 'use_reentrant_ckpt', 'set_reentrant_ckpt',
+    'use_fused_rope', 'set_fused_rope',
 ]
 
 # module-level state
@@ -22,6 +23,9 @@ _SCRIPTABLE = False
 
 # 0 == off, 1 == on (fused HIP kernel when available on device)
 _USE_FUSED_ATTN = int(os.environ.get('TIMM_AMD_FUSED_ATTN', os.environ.get('TIMM_FUSED_ATTN', '1')))
+
+# None == follow TIMM_AMD_FUSED_ROPE (read at call time, default on)
+_USE_FUSED_ROPE: Optional[bool] = None
 
 _USE_REENTRANT_CKPT = False
 
@@ -65,6 +69,22 @@ def use_fused_attn(experimental: bool = False) -> bool:
 def set_fused_attn(enable: bool = True, experimental: bool = False):
     global _USE_FUSED_ATTN
     _USE_FUSED_ATTN = 1 if enable else 0
+
+
+def use_fused_rope() -> bool:
+    """Gates the fused q/k rotary-embedding op in EvaAttention / AttentionRope.
+    Checked on every forward, so it can be toggled within one process."""
+    if _EXPORTABLE or _SCRIPTABLE or _NO_JIT:
+        return False
+    if _USE_FUSED_ROPE is not None:
+        return _USE_FUSED_ROPE
+    return int(os.environ.get('TIMM_AMD_FUSED_ROPE', '1')) > 0
+
+
+def set_fused_rope(enable: Optional[bool] = True):
+    """True/False overrides TIMM_AMD_FUSED_ROPE; None follows it again."""
+    global _USE_FUSED_ROPE
+    _USE_FUSED_ROPE = None if enable is None else bool(enable)
 
 
 def use_reentrant_ckpt() -> bool:

@@ -23,7 +23,7 @@ from ..layers import (
     AttentionPoolLatent, DropPath, GluMlp, LayerNorm, Mlp, PatchDropout, PatchEmbed, RmsNorm,
     RotaryEmbeddingCat, SwiGLU, apply_keep_indices_nlc, apply_rot_embed_cat, calculate_drop_path_rates,
     get_act_layer, get_norm_layer, resample_abs_pos_embed, resample_patch_embed, to_2tuple, trunc_normal_,
-    use_fused_attn, create_rope_embed, AttentionRope,
+    use_fused_attn, use_fused_rope, create_rope_embed, AttentionRope,
 )
 from ._builder import build_model_with_cfg
 from ._features import feature_take_indices
@@ -119,8 +119,13 @@ class EvaAttention(nn.Module):
         if rope is not None:
             npt = self.num_prefix_tokens
             half = self.rotate_half
-            q = torch.cat([q[:, :, :npt, :], apply_rot_embed_cat(q[:, :, npt:, :], rope, half=half)], 2).type_as(v)
-            k = torch.cat([k[:, :, :npt, :], apply_rot_embed_cat(k[:, :, npt:, :], rope, half=half)], 2).type_as(v)
+            if use_fused_rope():
+                q, k = ops.apply_rope_qk(q, k, rope, num_prefix_tokens=npt, half=half, out_dtype=v.dtype)
+            else:
+                q = torch.cat(
+                    [q[:, :, :npt, :], apply_rot_embed_cat(q[:, :, npt:, :], rope, half=half)], 2).type_as(v)
+                k = torch.cat(
+                    [k[:, :, :npt, :], apply_rot_embed_cat(k[:, :, npt:, :], rope, half=half)], 2).type_as(v)
 
         if self.fused_attn:
             x = ops.flash_attention(
@@ -602,6 +607,9 @@ class Eva(nn.Module):
             x, keep_indices = self.patch_drop(x)
             if rot_pos_embed is not None and keep_indices is not None:
                 rot_pos_embed = apply_keep_indices_nlc(x, rot_pos_embed, keep_indices)
+                if not self.rope_mixed:
+                    # per-sample table: [B, N, 2D] -> [B, 1, N, 2D] so it broadcasts over heads
+                    rot_pos_embed = rot_pos_embed.unsqueeze(1)
         return x, rot_pos_embed
 
     def forward_intermediates(

@@ -10,6 +10,7 @@ hand-written CDNA4 (gfx950) HIP kernel compiled into the in-tree extension
  * bias_act (bias+GELU/SiLU epilogue after GEMM)
  * residual add (+ LayerScale + DropPath) epilogue
  * multi-tensor fused optimizer steps (AdamW/LAMB/SGD/lerp-EMA)
+ * apply_rope_qk (rotary embedding of q and k, fwd/bwd) — one launch for both tensors
 
 Dispatch rules:
  * CUDA/ROCm tensor + extension available  -> HIP kernel.
@@ -74,6 +75,7 @@ from .elementwise import bias_act, residual_scale_add  # noqa: E402
 from .fused_optim import fused_adamw_step, fused_lamb_step, fused_lerp_, fused_l2norm  # noqa: E402
 from .loss import fused_cross_entropy  # noqa: E402
 from .data import u8_normalize, masked_global_pool  # noqa: E402
+from .rope import apply_rope_qk, rope_available  # noqa: E402
 
 __all__ = [
     'has_ext', 'require_ext', 'use_hip',
@@ -83,4 +85,5 @@ __all__ = [
     'bias_act', 'residual_scale_add',
     'fused_adamw_step', 'fused_lamb_step', 'fused_lerp_', 'fused_l2norm',
     'fused_cross_entropy', 'u8_normalize', 'masked_global_pool',
+    'apply_rope_qk', 'rope_available',
 ]

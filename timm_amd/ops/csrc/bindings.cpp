@@ -59,6 +59,10 @@ at::Tensor u8_normalize(at::Tensor x, at::Tensor mean, at::Tensor inv_std, at::S
 std::vector<at::Tensor> masked_pool_fwd(at::Tensor x, at::Tensor valid, bool is_max);
 at::Tensor masked_pool_bwd(at::Tensor dy, at::Tensor valid, at::Tensor aux, long n_tokens, bool is_max);
 
+// rope.hip
+std::vector<at::Tensor> rope_qk(at::Tensor q, at::Tensor k, at::Tensor rope,
+                                long npt, bool half, bool bwd, at::ScalarType out_dtype);
+
 // multi_tensor.hip
 void multi_tensor_adamw(
     std::vector<at::Tensor> params, std::vector<at::Tensor> grads,
@@ -96,6 +100,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("u8_normalize", &u8_normalize, "fused uint8 -> normalized tensor (loader prefetch)");
   m.def("masked_pool_fwd", &masked_pool_fwd, "masked global pool fwd (NaFlex)");
   m.def("masked_pool_bwd", &masked_pool_bwd, "masked global pool bwd (NaFlex)");
+  m.def("rope_qk", &rope_qk, "fused rotary embedding of q and k, fwd/bwd (gfx950)");
   m.def("multi_tensor_adamw", &multi_tensor_adamw, "fused multi-tensor AdamW step");
   m.def("multi_tensor_lerp", &multi_tensor_lerp, "fused multi-tensor lerp (EMA)");
   m.def("multi_tensor_lamb", &multi_tensor_lamb, "fused multi-tensor LAMB step (trust-ratio, gfx950)");
