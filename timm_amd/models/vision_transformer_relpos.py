@@ -12,6 +12,7 @@ from typing import List, Optional, Tuple, Type, Union
 import torch
 import torch.nn as nn
 
+from .. import ops
 from ..data.constants import IMAGENET_DEFAULT_MEAN, IMAGENET_DEFAULT_STD, IMAGENET_INCEPTION_MEAN, IMAGENET_INCEPTION_STD
 from ..layers import DropPath, LayerScale, Mlp, PatchEmbed, RelPosBias, RelPosMlp, trunc_normal_
 from ._builder import build_model_with_cfg
@@ -54,7 +55,9 @@ class RelPosAttention(nn.Module):
             attn_bias = shared_rel_pos
         else:
             attn_bias = None
-        x = torch.nn.functional.scaled_dot_product_attention(
+        # fused flash kernel takes the learned bias as an additive mask and
+        # returns its gradient; exact composition on CPU / unsupported shapes
+        x = ops.flash_attention(
             q, k, v, attn_mask=attn_bias,
             dropout_p=self.attn_drop.p if self.training else 0.)
 

@@ -7,6 +7,7 @@ hand-written CDNA4 (gfx950) HIP kernel compiled into the in-tree extension
 
  * layer_norm / rms_norm (+LayerScale fusion)          — fused one-pass, fp32 accum
  * attention (flash-style fused SDPA, bf16/fp16)       — MFMA 16x16x32, online softmax
+ * attention bias gradient (learned rel-pos bias)      — flash dBias pass, fp32, no atomics
  * bias_act (bias+GELU/SiLU epilogue after GEMM)
  * residual add (+ LayerScale + DropPath) epilogue
  * multi-tensor fused optimizer steps (AdamW/LAMB/SGD/lerp-EMA)

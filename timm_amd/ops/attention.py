@@ -12,6 +12,16 @@ directions are hand-written flash-style gfx950 HIP kernels:
    accumulated in fp32 MFMA registers, no [B,H,Nq,Nk] tensor ever touches
    HBM.  (The round-1 hipBLASLt GEMM-recompute chain remains available via
    TIMM_AMD_ATTN_BWD=gemm for A/B comparison.)
+ * bias gradient: when the additive mask requires grad (learned rel-pos bias
+   of Swin / BEiT / vit_relpos / ...), a third flash pass (attn_bwd_dbias
+   kernel) recomputes P and dP per 64x64 tile and sums the unscaled
+   dS = P o (dP - delta) in fp32 registers over the batches (and heads) that
+   share a bias element.  The batch loop is split over the grid into fp32
+   slabs that a small kernel sums in a fixed order - no atomics, so the
+   result is bit-reproducible.  Masks that need no gradient (padding masks,
+   inference) cost no extra launch or allocation.  Broadcast shapes are
+   reduced by autograd through `_prep_mask`, which stays outside the
+   autograd Function.
  * flash_attention_qkv: packed-qkv entry — takes the [B,N,3,H,D] projection
    output directly and writes gradients into one packed dqkv buffer, so the
    qkv-unbind `aten::copy_`/stack grad chain never appears in the graph.
@@ -38,12 +48,20 @@ def attention_available(q: torch.Tensor) -> bool:
     return D <= 128 and D % 32 == 0 and q.dtype == torch.bfloat16
 
 
+def _cyclic_mask(attn_mask, B):
+    """The kernels read a [mB,...] mask with 1 < mB < B, B % mB == 0 as
+    mask[b % mB] (Swin shift masks); the compositions take the same layout."""
+    if attn_mask.dim() == 4 and 1 < attn_mask.shape[0] < B and B % attn_mask.shape[0] == 0:
+        return attn_mask.repeat(B // attn_mask.shape[0], 1, 1, 1)
+    return attn_mask
+
+
 def _math_sdpa(q, k, v, attn_mask=None, scale=None):
     """Reference composition (matches F.scaled_dot_product_attention semantics)."""
     scale = scale if scale is not None else 1.0 / math.sqrt(q.shape[-1])
     attn = (q.float() @ k.float().transpose(-2, -1)) * scale
     if attn_mask is not None:
-        attn = attn + attn_mask.float()
+        attn = attn + _cyclic_mask(attn_mask, q.shape[0]).float()
     attn = attn.softmax(dim=-1)
     out = attn @ v.float()
     return out.to(q.dtype)
@@ -64,18 +82,71 @@ def _prep_mask(attn_mask, q, k):
     return attn_mask.contiguous().to(torch.float32)
 
 
-def _fused_backward(ext, q, k, v, o, lse, do, attn_mask, scale, dq, dk, dv):
-    """Shared fused-backward driver writing into preallocated dq/dk/dv."""
+# dBias pass split heuristic (see profiles/attn_dbias/README.md for the sweep):
+# aim for _DBIAS_TARGET_BLOCKS blocks in the grid (a few per CU on 256 CUs),
+# give every split at least _DBIAS_MIN_CHUNK reduced (batch, head) pairs so the
+# slab write and the second kernel stay small next to the loop, and keep the
+# fp32 slab workspace under _DBIAS_MAX_WORKSPACE bytes.
+_DBIAS_TARGET_BLOCKS = 1024
+_DBIAS_MIN_CHUNK = 4
+_DBIAS_MAX_WORKSPACE = 64 << 20
+_DBIAS_NSPLIT_FORCED: Optional[int] = None
+
+
+def set_dbias_nsplit(nsplit: Optional[int] = None):
+    """Force the dBias split count (tools/bench_attn_bias.py sweeps it);
+    None goes back to the heuristic."""
+    global _DBIAS_NSPLIT_FORCED
+    _DBIAS_NSPLIT_FORCED = None if nsplit is None else max(int(nsplit), 1)
+
+
+def _dbias_nsplit(n_red: int, n_tiles: int, slab_bytes: int) -> int:
+    """Number of chunks the dBias reduction loop is cut into.
+
+    n_red: (batch, head) pairs summed into one bias element,
+    n_tiles: 64x64 output tiles of the whole bias (= blocks at nsplit 1),
+    slab_bytes: size of one fp32 copy of the bias gradient.
+    """
+    if n_red <= 1:
+        return 1
+    nsplit = -(-_DBIAS_TARGET_BLOCKS // max(n_tiles, 1))
+    nsplit = min(nsplit, n_red // _DBIAS_MIN_CHUNK,
+                 max(_DBIAS_MAX_WORKSPACE // max(slab_bytes, 1), 1))
+    if nsplit <= 1:
+        return 1
+    chunk = -(-n_red // nsplit)
+    return -(-n_red // chunk)  # drop chunks that would be empty
+
+
+def _mask_nsplit(q, k, attn_mask) -> int:
+    if _DBIAS_NSPLIT_FORCED is not None:
+        return _DBIAS_NSPLIT_FORCED
+    B, H, Nq = q.shape[:3]
+    Nk = k.shape[2]
+    mB, Hm = attn_mask.shape[:2]
+    n_red = (B // mB) * (H if Hm == 1 else 1)
+    n_tiles = mB * Hm * (-(-Nq // 64)) * (-(-Nk // 64))
+    return _dbias_nsplit(n_red, n_tiles, mB * Hm * Nq * Nk * 4)
+
+
+def _fused_backward(ext, q, k, v, o, lse, do, attn_mask, scale, dq, dk, dv, need_dbias=False):
+    """Shared fused-backward driver writing into preallocated dq/dk/dv.
+    Returns the fp32 mask gradient when `need_dbias`, else None."""
     if do.dim() == 4 and do.stride(-1) == 1 and do.shape[-1] % 32 == 0 and do.shape[-1] <= 128:
         do_c, delta = ext.attn_bwd_preprocess(do, o)
     else:
         do_c = do.contiguous()
         delta = (do_c * o).float().sum(-1)
     ext.attention_bwd(q, k, v, do_c, lse, delta, attn_mask, dq, dk, dv, scale)
+    if need_dbias:
+        return ext.attention_bwd_dbias(
+            q, k, v, do_c, lse, delta, attn_mask, scale, _mask_nsplit(q, k, attn_mask))
+    return None
 
 
-def _gemm_backward(ext, q, k, v, o, lse, do, attn_mask, scale):
-    """Round-1 exact recompute via hipBLASLt GEMMs (A/B reference path)."""
+def _gemm_backward(ext, q, k, v, o, lse, do, attn_mask, scale, need_dbias=False):
+    """Round-1 exact recompute via hipBLASLt GEMMs (A/B reference path).
+    The mask gradient comes from the same dBias kernel as the fused path."""
     if do.dim() == 4 and do.stride(-1) == 1 and do.shape[-1] % 32 == 0 and do.shape[-1] <= 128:
         do, delta = ext.attn_bwd_preprocess(do, o)
     else:
@@ -88,7 +159,11 @@ def _gemm_backward(ext, q, k, v, o, lse, do, attn_mask, scale):
     ds = ext.attn_bwd_ds(p, dp, delta, scale)
     dq = ds @ k
     dk = ds.transpose(-2, -1) @ q
-    return dq, dk, dv
+    dbias = None
+    if need_dbias:
+        dbias = ext.attention_bwd_dbias(
+            q, k, v, do, lse, delta, attn_mask, scale, _mask_nsplit(q, k, attn_mask))
+    return dq, dk, dv, dbias
 
 
 class _FlashAttnFn(torch.autograd.Function):
@@ -116,14 +191,17 @@ class _FlashAttnFn(torch.autograd.Function):
         q, k, v, o, lse = ctx.saved_tensors
         ext = _load_extension()
         scale = ctx.scale
+        need_dbias = ctx.attn_mask is not None and ctx.needs_input_grad[3]
         if _BWD_MODE == 'gemm':
-            dq, dk, dv = _gemm_backward(ext, q, k, v, o, lse, do, ctx.attn_mask, scale)
+            dq, dk, dv, dbias = _gemm_backward(
+                ext, q, k, v, o, lse, do, ctx.attn_mask, scale, need_dbias)
         else:
             dq = torch.empty_like(q, memory_format=torch.contiguous_format)
             dk = torch.empty_like(k, memory_format=torch.contiguous_format)
             dv = torch.empty_like(v, memory_format=torch.contiguous_format)
-            _fused_backward(ext, q, k, v, o, lse, do, ctx.attn_mask, scale, dq, dk, dv)
-        return dq, dk, dv, None, None
+            dbias = _fused_backward(
+                ext, q, k, v, o, lse, do, ctx.attn_mask, scale, dq, dk, dv, need_dbias)
+        return dq, dk, dv, dbias, None
 
 
 class _FlashAttnQkvFn(torch.autograd.Function):
@@ -156,8 +234,10 @@ class _FlashAttnQkvFn(torch.autograd.Function):
         dq = dqkv[:, :, 0].permute(0, 2, 1, 3)
         dk = dqkv[:, :, 1].permute(0, 2, 1, 3)
         dv = dqkv[:, :, 2].permute(0, 2, 1, 3)
-        _fused_backward(ext, q, k, v, o, lse, do, ctx.attn_mask, ctx.scale, dq, dk, dv)
-        return dqkv, None, None
+        need_dbias = ctx.attn_mask is not None and ctx.needs_input_grad[1]
+        dbias = _fused_backward(
+            ext, q, k, v, o, lse, do, ctx.attn_mask, ctx.scale, dq, dk, dv, need_dbias)
+        return dqkv, dbias, None
 
 
 def flash_attention(
@@ -216,7 +296,7 @@ def flash_attention_qkv(
 def _dropout_sdpa(q, k, v, attn_mask, dropout_p, scale):
     attn = (q @ k.transpose(-2, -1)) * scale
     if attn_mask is not None:
-        attn = attn + attn_mask
+        attn = attn + _cyclic_mask(attn_mask, q.shape[0])
     attn = attn.softmax(dim=-1)
     attn = F.dropout(attn, p=dropout_p, training=True)
     return attn @ v

@@ -422,6 +422,152 @@ void attn_bwd_dkdv_kernel(
   }
 }
 
+// ---------------------------------------------------------------------------
+// dBias pass: gradient of the additive mask/bias, dBias = sum over the batches
+// and heads that share a bias element of the unscaled dS = P o (dP - delta).
+// A block owns one (m, h', 64-row q tile, 64-col kv tile) output tile (wave w
+// -> rows [w*16, w*16+16), 4 f32x4 accumulators) and loops over the (b, h)
+// pairs that reduce into it: b = m + i*mB, and every head when Hm == 1.  The
+// loop is cut into gridDim.z chunks; chunk z writes slab z of
+// [nsplit, mB, Hm, Nq, Nk] with plain stores (no float atomics, so the result
+// is bit-reproducible) and attn_bwd_dbias_reduce_kernel sums the slabs in
+// order.  dS stays fp32 from the MFMA accumulators to the store: it never
+// goes through LDS, the C layout is the store layout.
+// ---------------------------------------------------------------------------
+template <int kMaxD, bool kSwizzle>
+__global__ __launch_bounds__(kBlockThreads)
+void attn_bwd_dbias_kernel(
+    const __bf16* __restrict__ q,     // [B,H,Nq,D] strided
+    const __bf16* __restrict__ k,     // [B,H,Nk,D] strided
+    const __bf16* __restrict__ v,     // [B,H,Nk,D] strided
+    const __bf16* __restrict__ dov,   // [B,H,Nq,D] contiguous
+    const float* __restrict__ lse,    // [B,H,Nq]
+    const float* __restrict__ delta,  // [B,H,Nq]
+    const float* __restrict__ mask,   // [mB,Hm,Nq,Nk] contiguous
+    float* __restrict__ out,          // [nsplit,mB,Hm,Nq,Nk]
+    int H, int Nq, int Nk, int D, float scale,
+    int mB, int Hm, int n_kt, int n_red, int chunk,
+    long q_sb, long q_sh, long q_sn,
+    long k_sb, long k_sh, long k_sn,
+    long v_sb, long v_sh, long v_sn) {
+  constexpr int kTile = 64;
+  __shared__ __bf16 q_lds[kTile * kMaxD];
+  __shared__ __bf16 do_lds[kTile * kMaxD];
+  __shared__ __bf16 k_lds[kTile * kMaxD];
+  __shared__ __bf16 v_lds[kTile * kMaxD];
+
+  const int tiles = gridDim.x / (mB * Hm);
+  const int tile = blockIdx.x % tiles;
+  const int mh = blockIdx.x / tiles;
+  const int m = mh / Hm;
+  const int hm = mh % Hm;
+  const int qbase = (tile / n_kt) * kTile;
+  const int kvbase = (tile % n_kt) * kTile;
+  const int nh = (Hm == 1) ? H : 1;  // heads reduced into this tile
+  const int wave = threadIdx.x / WAVE_SIZE;
+  const int lane = threadIdx.x % WAVE_SIZE;
+  const int l16 = lane & 15;
+  const int g4 = lane >> 4;
+  const int d8 = D / 8;
+
+  // the bias tile is the same for every reduced (b, h): read it once
+  const long mh_off = (long)mh * Nq * Nk;
+  float bias_r[4][4];
+#pragma unroll
+  for (int n16 = 0; n16 < 4; ++n16) {
+    const int kvcol = kvbase + n16 * 16 + l16;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int qrow = qbase + wave * 16 + g4 * 4 + r;
+      bias_r[n16][r] = (qrow < Nq && kvcol < Nk)
+          ? mask[mh_off + (long)qrow * Nk + kvcol] : 0.f;
+    }
+  }
+
+  f32x4 acc[4];
+#pragma unroll
+  for (int n16 = 0; n16 < 4; ++n16) acc[n16] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  const int r_begin = blockIdx.z * chunk;
+  const int r_end = min(n_red, r_begin + chunk);
+  for (int ri = r_begin; ri < r_end; ++ri) {
+    const int b = m + (ri / nh) * mB;
+    const int h = (Hm == 1) ? (ri % nh) : hm;
+    const long bh = (long)b * H + h;
+
+    float lse_r[4], delta_r[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int qrow = qbase + wave * 16 + g4 * 4 + r;
+      lse_r[r] = (qrow < Nq) ? lse[bh * Nq + qrow] : INFINITY;
+      delta_r[r] = (qrow < Nq) ? delta[bh * Nq + qrow] : 0.f;
+    }
+
+    __syncthreads();  // previous iteration's reads done before restage
+    stage_tile<kSwizzle>(q_lds, q + (long)b * q_sb + (long)h * q_sh, q_sn,
+                         qbase, kTile, Nq, D, d8);
+    stage_tile<kSwizzle>(do_lds, dov + (bh * Nq) * D, D, qbase, kTile, Nq, D, d8);
+    stage_tile<kSwizzle>(k_lds, k + (long)b * k_sb + (long)h * k_sh, k_sn,
+                         kvbase, kTile, Nk, D, d8);
+    stage_tile<kSwizzle>(v_lds, v + (long)b * v_sb + (long)h * v_sh, v_sn,
+                         kvbase, kTile, Nk, D, d8);
+    __syncthreads();
+
+#pragma unroll
+    for (int n16 = 0; n16 < 4; ++n16) {
+      f32x4 acc_s = {0.f, 0.f, 0.f, 0.f};
+      f32x4 acc_dp = {0.f, 0.f, 0.f, 0.f};
+      for (int d0 = 0; d0 < D; d0 += 32) {
+        bf16x8_t qa = frag_row<kSwizzle>(q_lds, wave * 16 + l16, d0, g4, D);
+        bf16x8_t kb = frag_row<kSwizzle>(k_lds, n16 * 16 + l16, d0, g4, D);
+        acc_s = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qa, kb, acc_s, 0, 0, 0);
+        bf16x8_t da = frag_row<kSwizzle>(do_lds, wave * 16 + l16, d0, g4, D);
+        bf16x8_t vb = frag_row<kSwizzle>(v_lds, n16 * 16 + l16, d0, g4, D);
+        acc_dp = __builtin_amdgcn_mfma_f32_16x16x32_bf16(da, vb, acc_dp, 0, 0, 0);
+      }
+      const int kvcol = kvbase + n16 * 16 + l16;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int qrow = qbase + wave * 16 + g4 * 4 + r;
+        float s = acc_s[r] * scale;
+        if (kvcol >= Nk || qrow >= Nq) {
+          s = kNegInf;
+        } else {
+          s += bias_r[n16][r];
+          if (s < kNegInf) s = kNegInf;
+        }
+        const float p = (s <= kNegInf) ? 0.f : __expf(s - lse_r[r]);
+        acc[n16][r] += p * (acc_dp[r] - delta_r[r]);
+      }
+    }
+  }
+
+  // C layout is the store layout: row = wave*16 + g4*4 + r, col = n16*16 + l16
+  float* out_t = out + ((long)blockIdx.z * mB * Hm + mh) * Nq * Nk;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int qrow = qbase + wave * 16 + g4 * 4 + r;
+    if (qrow >= Nq) continue;
+#pragma unroll
+    for (int n16 = 0; n16 < 4; ++n16) {
+      const int kvcol = kvbase + n16 * 16 + l16;
+      if (kvcol < Nk) out_t[(long)qrow * Nk + kvcol] = acc[n16][r];
+    }
+  }
+}
+
+// Sum the nsplit slabs of the dBias pass in slab order (fixed order -> same
+// bits every run).
+__global__ __launch_bounds__(kBlockThreads)
+void attn_bwd_dbias_reduce_kernel(
+    const float* __restrict__ slabs, float* __restrict__ out, long n, int nsplit) {
+  const long i = (long)blockIdx.x * kBlockThreads + threadIdx.x;
+  if (i >= n) return;
+  float acc = 0.f;
+  for (int z = 0; z < nsplit; ++z) acc += slabs[(long)z * n + i];
+  out[i] = acc;
+}
+
 struct MaskInfo {
   const float* ptr = nullptr;
   int mB = 1;
@@ -492,6 +638,37 @@ void launch_attn_bwd(
   HIP_CHECK_LAST();
 }
 
+template <int kMaxD>
+void launch_attn_bwd_dbias(
+    const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
+    const at::Tensor& dov, const at::Tensor& lse, const at::Tensor& delta,
+    const at::Tensor& mask, float* out,
+    int H, int Nq, int Nk, int D, float scale,
+    int n_red, int chunk, int nsplit, hipStream_t stream) {
+  const MaskInfo mi = mask_info(mask, Nq, Nk);
+  const int Hm = (int)mask.size(1);
+  const int n_kt = cdiv(Nk, 64);
+  const bool swizzle = (D == 64 || D == 128);
+  dim3 block(kBlockThreads);
+  dim3 grid(cdiv(Nq, 64) * n_kt * mi.mB * Hm, 1, nsplit);
+  auto run = [&](auto kern) {
+    hipLaunchKernelGGL(kern, grid, block, 0, stream,
+        (const __bf16*)q.data_ptr(), (const __bf16*)k.data_ptr(), (const __bf16*)v.data_ptr(),
+        (const __bf16*)dov.data_ptr(), lse.data_ptr<float>(), delta.data_ptr<float>(),
+        mi.ptr, out,
+        H, Nq, Nk, D, scale, mi.mB, Hm, n_kt, n_red, chunk,
+        q.stride(0), q.stride(1), q.stride(2),
+        k.stride(0), k.stride(1), k.stride(2),
+        v.stride(0), v.stride(1), v.stride(2));
+  };
+  if (swizzle) {
+    run(attn_bwd_dbias_kernel<kMaxD, true>);
+  } else {
+    run(attn_bwd_dbias_kernel<kMaxD, false>);
+  }
+  HIP_CHECK_LAST();
+}
+
 }  // namespace
 
 // Full fused backward.  q/k/v strided [B,H,N,D] (head_dim contiguous);
@@ -530,4 +707,71 @@ void attention_bwd(at::Tensor q, at::Tensor k, at::Tensor v,
     launch_attn_bwd<128>(q, k, v, dov, lse, delta, mask, dq, dk, dv, B, H, Nq, Nk, D,
                          (float)scale, stream);
   }
+}
+
+// Gradient of the additive mask/bias: fp32, the mask's shape [mB,Hm,Nq,Nk].
+// Inputs as for attention_bwd.  `nsplit` cuts the reduction over the
+// (B/mB) * (Hm == 1 ? H : 1) batch/head pairs that share a bias element into
+// that many chunks (clamped to the pair count); each chunk writes an fp32 slab
+// and a second kernel sums the slabs in order.
+at::Tensor attention_bwd_dbias(at::Tensor q, at::Tensor k, at::Tensor v,
+                               at::Tensor dov, at::Tensor lse, at::Tensor delta,
+                               at::Tensor mask, double scale, int64_t nsplit) {
+  TORCH_CHECK(q.is_cuda() && q.dim() == 4 && q.scalar_type() == at::kBFloat16);
+  TORCH_CHECK(k.is_cuda() && k.dim() == 4 && k.scalar_type() == at::kBFloat16 &&
+              v.is_cuda() && v.dim() == 4 && v.scalar_type() == at::kBFloat16 &&
+              dov.is_cuda() && dov.scalar_type() == at::kBFloat16);
+  TORCH_CHECK(q.stride(3) == 1 && k.stride(3) == 1 && v.stride(3) == 1,
+              "attention_bwd_dbias: head_dim stride must be 1");
+  TORCH_CHECK(dov.is_contiguous(), "attention_bwd_dbias: dO must be contiguous");
+  int B = q.size(0), H = q.size(1), Nq = q.size(2), D = q.size(3);
+  int Nk = k.size(2);
+  TORCH_CHECK(D % 32 == 0 && D <= 128, "attention_bwd_dbias: head_dim multiple of 32, <=128");
+  TORCH_CHECK(k.size(0) == B && k.size(1) == H && k.size(3) == D &&
+              v.size(0) == B && v.size(1) == H && v.size(2) == Nk && v.size(3) == D &&
+              dov.sizes() == q.sizes(), "attention_bwd_dbias: q/k/v/dO shapes disagree");
+  const long rows = (long)B * H * Nq;
+  TORCH_CHECK(lse.is_cuda() && lse.is_contiguous() && lse.scalar_type() == at::kFloat &&
+              lse.numel() == rows && delta.is_cuda() && delta.is_contiguous() &&
+              delta.scalar_type() == at::kFloat && delta.numel() == rows,
+              "attention_bwd_dbias: lse/delta must be contiguous fp32 [B,H,Nq]");
+  TORCH_CHECK(mask.is_cuda() && mask.dim() == 4 && mask.is_contiguous() &&
+              mask.scalar_type() == at::kFloat);
+  TORCH_CHECK(mask.size(0) >= 1 && B % mask.size(0) == 0 &&
+              (mask.size(1) == H || mask.size(1) == 1) &&
+              mask.size(2) == Nq && mask.size(3) == Nk);
+  at::Tensor dbias = at::empty_like(mask);
+  if (dbias.numel() == 0) return dbias;
+  const int n_red = (B / (int)mask.size(0)) * (mask.size(1) == 1 ? H : 1);
+  int ns = (int)std::min<int64_t>(std::max<int64_t>(nsplit, 1), std::min(n_red, 65535));
+  const int chunk = cdiv(n_red, ns);
+  ns = cdiv(n_red, chunk);  // no empty chunks
+  at::Tensor slabs;
+  float* out = dbias.data_ptr<float>();
+  if (ns > 1) {
+    slabs = at::empty({(int64_t)ns * dbias.numel()}, dbias.options());
+    out = slabs.data_ptr<float>();
+  }
+  auto stream = at::hip::getCurrentHIPStream();
+  if (D <= 32) {
+    launch_attn_bwd_dbias<32>(q, k, v, dov, lse, delta, mask, out, H, Nq, Nk, D,
+                              (float)scale, n_red, chunk, ns, stream);
+  } else if (D <= 64) {
+    launch_attn_bwd_dbias<64>(q, k, v, dov, lse, delta, mask, out, H, Nq, Nk, D,
+                              (float)scale, n_red, chunk, ns, stream);
+  } else if (D <= 96) {
+    launch_attn_bwd_dbias<96>(q, k, v, dov, lse, delta, mask, out, H, Nq, Nk, D,
+                              (float)scale, n_red, chunk, ns, stream);
+  } else {
+    launch_attn_bwd_dbias<128>(q, k, v, dov, lse, delta, mask, out, H, Nq, Nk, D,
+                               (float)scale, n_red, chunk, ns, stream);
+  }
+  if (ns > 1) {
+    const long n = dbias.numel();
+    hipLaunchKernelGGL(attn_bwd_dbias_reduce_kernel,
+        dim3((unsigned)((n + kBlockThreads - 1) / kBlockThreads)), dim3(kBlockThreads),
+        0, stream, slabs.data_ptr<float>(), dbias.data_ptr<float>(), n, ns);
+    HIP_CHECK_LAST();
+  }
+  return dbias;
 }

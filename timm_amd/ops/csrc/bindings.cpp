@@ -33,6 +33,9 @@ void attention_bwd(at::Tensor q, at::Tensor k, at::Tensor v,
                    c10::optional<at::Tensor> mask,
                    at::Tensor dq, at::Tensor dk, at::Tensor dv,
                    double scale);
+at::Tensor attention_bwd_dbias(at::Tensor q, at::Tensor k, at::Tensor v,
+                               at::Tensor dov, at::Tensor lse, at::Tensor delta,
+                               at::Tensor mask, double scale, int64_t nsplit);
 
 // depthwise_conv.hip
 at::Tensor dwconv_fwd(at::Tensor x, at::Tensor w_t, c10::optional<at::Tensor> bias,
@@ -90,6 +93,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_bwd_ds", &attn_bwd_ds, "fused dS epilogue for attention bwd");
   m.def("attn_bwd_preprocess", &attn_bwd_preprocess, "fused dO copy + delta for attention bwd");
   m.def("attention_bwd", &attention_bwd, "fused flash attention bwd (MFMA, gfx950)");
+  m.def("attention_bwd_dbias", &attention_bwd_dbias,
+        "fused flash attention bwd: gradient of the additive mask/bias (MFMA, gfx950)",
+        py::arg("q"), py::arg("k"), py::arg("v"), py::arg("dov"), py::arg("lse"),
+        py::arg("delta"), py::arg("mask"), py::arg("scale"), py::arg("nsplit") = 1);
   m.def("dwconv_fwd", &dwconv_fwd, "NHWC depthwise conv fwd (gfx950)");
   m.def("dwconv_bwd_data", &dwconv_bwd_data, "NHWC depthwise conv bwd-data");
   m.def("dwconv_bwd_weight", &dwconv_bwd_weight, "NHWC depthwise conv bwd-weight");
