@@ -5,7 +5,7 @@ see SURVEY.md §2.10 for the op-by-op map.  Here each of them dispatches to a
 hand-written CDNA4 (gfx950) HIP kernel compiled into the in-tree extension
 `timm_amd._C`:
 
- * layer_norm / rms_norm (+LayerScale fusion)          — fused one-pass, fp32 accum
+ * layer_norm / rms_norm (+LayerScale fusion)          — one read of x, two-pass fp32 statistics
  * attention (flash-style fused SDPA, bf16/fp16)       — MFMA 16x16x32, online softmax
  * attention bias gradient (learned rel-pos bias)      — flash dBias pass, fp32, no atomics
  * bias_act (bias+GELU/SiLU epilogue after GEMM)

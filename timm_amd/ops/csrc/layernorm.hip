@@ -2,8 +2,8 @@
 //
 // Replaces the reference's F.layer_norm / F.rms_norm hot path
 // (timm/layers/norm.py:70-290, fast_norm.py:119-160).
-// One wave per row (4 rows per 256-thread block), fp32 accumulation,
-// vectorized 16B (8 x bf16) loads per lane (guide §Guideline 13: scalar bf16
+// One wave per row (4 rows per 256-thread block), fp32 accumulation with a
+// cancellation-free two-pass variance, vectorized 16B (8 x bf16) loads per lane (guide §Guideline 13: scalar bf16
 // loads are ~2x slower). dW/dB reduced via fp32 atomics.
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
@@ -17,8 +17,109 @@ constexpr int kWavesPerBlock = kBlock / WAVE_SIZE;
 // ----------------------------------------------------------------------------
 // forward: y = (x - mean) * rstd * w + b ; saves mean, rstd (fp32 per row)
 // RMS variant: y = x * rstd * w (mean==0 fixed), saves rstd only.
+//
+// LayerNorm statistics use the corrected two-pass form: mean0 = sum(x)/n, then
+// d = x - mean0, s1 = sum(d), s2 = sum(d*d) in one more sweep, and
+//   mean = mean0 + s1/n,  var = s2/n - (s1/n)^2.
+// E[x^2] - mean^2 in fp32 loses every digit of the variance once |mean| >> std
+// (NaN from rsqrt of a negative variance on constant rows).  Here the only
+// subtraction left removes the square of mean0's own rounding error, and the
+// s1/n term repairs that error, so a constant row gets mean == x exactly.
 // ----------------------------------------------------------------------------
 
+__device__ __forceinline__ void norm_row_stats(float mean0, float s1, float s2, int cols, float eps,
+                                               float& mean, float& rstd) {
+  const float d = s1 / cols;
+  mean = mean0 + d;
+  rstd = rsqrtf(s2 / cols - d * d + eps);
+}
+
+// Register-resident forward for 16-bit types: each lane keeps its (up to
+// kChunks) 16B vectors of the row, so x is read from memory once for the
+// mean, the variance and the output.  Requires cols % 8 == 0 and
+// cols <= kChunks*512.
+template <typename T, bool kRms, int kChunks>
+__global__ __launch_bounds__(kBlock)
+void norm_fwd_reg_kernel(
+    const T* __restrict__ x,
+    const T* __restrict__ w,
+    const T* __restrict__ b,
+    T* __restrict__ y,
+    float* __restrict__ mean_out,
+    float* __restrict__ rstd_out,
+    int rows, int cols, float eps) {
+  const int wave = threadIdx.x / WAVE_SIZE;
+  const int lane = threadIdx.x % WAVE_SIZE;
+  const int nvec = cols / 8;
+  const short8* wv = reinterpret_cast<const short8*>(w);
+  const short8* bv = b ? reinterpret_cast<const short8*>(b) : nullptr;
+
+  for (int row = blockIdx.x * kWavesPerBlock + wave; row < rows;
+       row += gridDim.x * kWavesPerBlock) {
+    const short8* xv = reinterpret_cast<const short8*>(x + (long)row * cols);
+    short8* yv = reinterpret_cast<short8*>(y + (long)row * cols);
+
+    short8 v[kChunks];
+    float sum = 0.f;
+#pragma unroll
+    for (int c = 0; c < kChunks; ++c) {
+      int i = lane + c * WAVE_SIZE;
+      if (i < nvec) {
+        v[c] = xv[i];
+        if (!kRms) {
+#pragma unroll
+          for (int j = 0; j < 8; ++j) sum += Elem<T>::to_f32(reinterpret_cast<const T*>(&v[c])[j]);
+        }
+      }
+    }
+    const float mean0 = kRms ? 0.f : wave_reduce_sum(sum) / cols;
+
+    float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+    for (int c = 0; c < kChunks; ++c) {
+      int i = lane + c * WAVE_SIZE;
+      if (i < nvec) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          float d = Elem<T>::to_f32(reinterpret_cast<const T*>(&v[c])[j]) - mean0;
+          if (!kRms) s1 += d;
+          s2 += d * d;
+        }
+      }
+    }
+    s2 = wave_reduce_sum(s2);
+    if (!kRms) s1 = wave_reduce_sum(s1);
+    float mean, rstd;
+    norm_row_stats(mean0, s1, s2, cols, eps, mean, rstd);
+    if (lane == 0) {
+      if (!kRms && mean_out) mean_out[row] = mean;
+      rstd_out[row] = rstd;
+    }
+
+#pragma unroll
+    for (int c = 0; c < kChunks; ++c) {
+      int i = lane + c * WAVE_SIZE;
+      if (i < nvec) {
+        short8 wg = wv[i];
+        short8 bb;
+        if (bv) bb = bv[i];
+        short8 out;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          float f = Elem<T>::to_f32(reinterpret_cast<const T*>(&v[c])[j]);
+          float wf = Elem<T>::to_f32(reinterpret_cast<const T*>(&wg)[j]);
+          float o = (f - mean) * rstd * wf;
+          if (bv) o += Elem<T>::to_f32(reinterpret_cast<const T*>(&bb)[j]);
+          reinterpret_cast<T*>(&out)[j] = Elem<T>::from_f32(o);
+        }
+        yv[i] = out;
+      }
+    }
+  }
+}
+
+// Generic forward (fp32, cols % 8 != 0, or rows wider than the register
+// kernel holds): same statistics, the row is re-read from cache per sweep.
 template <typename T, bool kRms>
 __global__ void norm_fwd_kernel(
     const T* __restrict__ x,
@@ -30,50 +131,61 @@ __global__ void norm_fwd_kernel(
     int rows, int cols, float eps) {
   const int wave = threadIdx.x / WAVE_SIZE;
   const int lane = threadIdx.x % WAVE_SIZE;
-  const bool vec_ok = (cols % 8 == 0);
+  const bool vec = (cols % 8 == 0) && sizeof(T) == 2;
+  const int nvec = cols / 8;
 
   for (int row = blockIdx.x * kWavesPerBlock + wave; row < rows;
        row += gridDim.x * kWavesPerBlock) {
     const T* xr = x + (long)row * cols;
     T* yr = y + (long)row * cols;
+    const short8* xv = reinterpret_cast<const short8*>(xr);
 
-    float sum = 0.f, sumsq = 0.f;
-    if (vec_ok && sizeof(T) == 2) {
-      const short8* xv = reinterpret_cast<const short8*>(xr);
-      int nvec = cols / 8;
+    float mean0 = 0.f;
+    if (!kRms) {
+      float sum = 0.f;
+      if (vec) {
+        for (int i = lane; i < nvec; i += WAVE_SIZE) {
+          short8 v = xv[i];
+#pragma unroll
+          for (int j = 0; j < 8; ++j) sum += Elem<T>::to_f32(reinterpret_cast<const T*>(&v)[j]);
+        }
+      } else {
+        for (int i = lane; i < cols; i += WAVE_SIZE) sum += Elem<T>::to_f32(xr[i]);
+      }
+      mean0 = wave_reduce_sum(sum) / cols;
+    }
+
+    float s1 = 0.f, s2 = 0.f;
+    if (vec) {
       for (int i = lane; i < nvec; i += WAVE_SIZE) {
         short8 v = xv[i];
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-          float f = Elem<T>::to_f32(reinterpret_cast<const T*>(&v)[j]);
-          sum += f;
-          sumsq += f * f;
+          float d = Elem<T>::to_f32(reinterpret_cast<const T*>(&v)[j]) - mean0;
+          if (!kRms) s1 += d;
+          s2 += d * d;
         }
       }
     } else {
       for (int i = lane; i < cols; i += WAVE_SIZE) {
-        float f = Elem<T>::to_f32(xr[i]);
-        sum += f;
-        sumsq += f * f;
+        float d = Elem<T>::to_f32(xr[i]) - mean0;
+        if (!kRms) s1 += d;
+        s2 += d * d;
       }
     }
-    sum = wave_reduce_sum(sum);
-    sumsq = wave_reduce_sum(sumsq);
-
-    float mean = kRms ? 0.f : sum / cols;
-    float var = sumsq / cols - mean * mean;
-    float rstd = rsqrtf(var + eps);
+    s2 = wave_reduce_sum(s2);
+    if (!kRms) s1 = wave_reduce_sum(s1);
+    float mean, rstd;
+    norm_row_stats(mean0, s1, s2, cols, eps, mean, rstd);
     if (lane == 0) {
       if (!kRms && mean_out) mean_out[row] = mean;
       rstd_out[row] = rstd;
     }
 
-    if (vec_ok && sizeof(T) == 2) {
-      const short8* xv = reinterpret_cast<const short8*>(xr);
+    if (vec) {
       const short8* wv = reinterpret_cast<const short8*>(w);
       const short8* bv = b ? reinterpret_cast<const short8*>(b) : nullptr;
       short8* yv = reinterpret_cast<short8*>(yr);
-      int nvec = cols / 8;
       for (int i = lane; i < nvec; i += WAVE_SIZE) {
         short8 v = xv[i];
         short8 wg = wv[i];
@@ -293,21 +405,40 @@ void norm_bwd_fast_kernel(
   }
 }
 
+template <typename T, bool kRms>
+void launch_norm_fwd_t(const T* x, const T* w, const T* b, T* y, float* mean, float* rstd,
+                       int rows, int cols, float eps, hipStream_t stream) {
+  int blocks = std::min(cdiv(rows, kWavesPerBlock), 8192);
+  if constexpr (sizeof(T) == 2) {
+    const int chunks = cdiv(cols / 8, WAVE_SIZE);
+    if (cols % 8 == 0 && chunks <= 8) {
+      auto go = [&](auto tag) {
+        constexpr int kChunks = decltype(tag)::value;
+        hipLaunchKernelGGL((norm_fwd_reg_kernel<T, kRms, kChunks>),
+            dim3(blocks), dim3(kBlock), 0, stream, x, w, b, y, mean, rstd, rows, cols, eps);
+      };
+      if (chunks <= 1) go(std::integral_constant<int, 1>{});
+      else if (chunks <= 2) go(std::integral_constant<int, 2>{});
+      else if (chunks <= 4) go(std::integral_constant<int, 4>{});
+      else go(std::integral_constant<int, 8>{});
+      return;
+    }
+  }
+  hipLaunchKernelGGL((norm_fwd_kernel<T, kRms>), dim3(blocks), dim3(kBlock), 0, stream,
+      x, w, b, y, mean, rstd, rows, cols, eps);
+}
+
 template <typename T>
 void launch_norm_fwd(const at::Tensor& x, const at::Tensor& w, const c10::optional<at::Tensor>& b,
                      at::Tensor& y, at::Tensor& mean, at::Tensor& rstd, double eps, bool rms,
                      int rows, int cols, hipStream_t stream) {
-  int blocks = std::min(cdiv(rows, kWavesPerBlock), 8192);
+  const T* bp = b.has_value() ? (const T*)b->data_ptr() : nullptr;
   if (rms) {
-    hipLaunchKernelGGL((norm_fwd_kernel<T, true>), dim3(blocks), dim3(kBlock), 0, stream,
-        (const T*)x.data_ptr(), (const T*)w.data_ptr(),
-        b.has_value() ? (const T*)b->data_ptr() : nullptr,
-        (T*)y.data_ptr(), nullptr, rstd.data_ptr<float>(), rows, cols, (float)eps);
+    launch_norm_fwd_t<T, true>((const T*)x.data_ptr(), (const T*)w.data_ptr(), bp,
+        (T*)y.data_ptr(), nullptr, rstd.data_ptr<float>(), rows, cols, (float)eps, stream);
   } else {
-    hipLaunchKernelGGL((norm_fwd_kernel<T, false>), dim3(blocks), dim3(kBlock), 0, stream,
-        (const T*)x.data_ptr(), (const T*)w.data_ptr(),
-        b.has_value() ? (const T*)b->data_ptr() : nullptr,
-        (T*)y.data_ptr(), mean.data_ptr<float>(), rstd.data_ptr<float>(), rows, cols, (float)eps);
+    launch_norm_fwd_t<T, false>((const T*)x.data_ptr(), (const T*)w.data_ptr(), bp,
+        (T*)y.data_ptr(), mean.data_ptr<float>(), rstd.data_ptr<float>(), rows, cols, (float)eps, stream);
   }
   HIP_CHECK_LAST();
 }

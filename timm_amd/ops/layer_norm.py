@@ -2,7 +2,9 @@
 
 Replaces the reference's `F.layer_norm`/`F.rms_norm` hot path
 (`timm/layers/norm.py:70-290`, `timm/layers/fast_norm.py:119-160`) with a
-single-pass gfx950 HIP kernel (fp32 accumulators, vectorized bf16 loads).
+gfx950 HIP kernel: the row is read once into registers, fp32 statistics use
+the corrected two-pass form (mean first, then sums of x - mean), so rows with
+|mean| >> std keep their variance.
 CPU path uses the plain PyTorch composition and serves as the numerics
 reference for GPU tests.
 """
