@@ -7,11 +7,24 @@ directions are hand-written flash-style gfx950 HIP kernels:
  * forward: MFMA 16x16x32 bf16 QK^T + online softmax + PV, returns O and
    logsumexp (LSE) per row.  Supports optional additive mask (NaFlex padding
    masks, rel-pos bias broadcast over batch).
- * backward: fused two-pass flash backward (attn_bwd_dq / attn_bwd_dkdv
-   kernels) — softmax recomputed from LSE inside the tile loop, dQ/dK/dV
-   accumulated in fp32 MFMA registers, no [B,H,Nq,Nk] tensor ever touches
-   HBM.  (The round-1 hipBLASLt GEMM-recompute chain remains available via
-   TIMM_AMD_ATTN_BWD=gemm for A/B comparison.)
+ * backward: fused flash backward — softmax recomputed from LSE inside the
+   tile loop, dQ/dK/dV accumulated in fp32 MFMA registers, no [B,H,Nq,Nk]
+   tensor ever touches HBM.  Two implementations, chosen per call by
+   `_select_bwd_path` (rule and numbers next to it):
+     - single-pass (attn_bwd_single_pass kernel): head_dim 64 and
+       49 <= Nk <= 256 (ViT / DeiT / BEiT at 224², windows of 49..144
+       tokens).  One workgroup per (batch, head) owns every key, S / dP / P /
+       dS are computed once, dK / dV stay in registers over the whole sweep
+       of the query rows, dQ is completed inside the workgroup (no atomics),
+       and delta = rowsum(dO o O) is formed in the kernel from strided dO
+       and O, so attn_bwd_preprocess is not launched unless a bias gradient
+       is wanted.
+     - two-pass (attn_bwd_dq / attn_bwd_dkdv kernels behind
+       attn_bwd_preprocess): everything else — Nk > 256, other head dims.
+   TIMM_AMD_ATTN_BWD=two_pass forces the two-pass kernels for a process,
+   `set_attn_bwd_path` forces either from code; the round-1 hipBLASLt
+   GEMM-recompute chain remains available via TIMM_AMD_ATTN_BWD=gemm for A/B
+   comparison (both entries).
  * bias gradient: when the additive mask requires grad (learned rel-pos bias
    of Swin / BEiT / vit_relpos / ...), a third flash pass (attn_bwd_dbias
    kernel) recomputes P and dP per 64x64 tile and sums the unscaled
@@ -129,15 +142,81 @@ def _mask_nsplit(q, k, attn_mask) -> int:
     return _dbias_nsplit(n_red, n_tiles, mB * Hm * Nq * Nk * 4)
 
 
+# Which fused backward runs (numbers: profiles/attn_bwd_single_pass/README.md):
+# the single-pass kernel (one workgroup per (batch, head) owns every key)
+# takes head_dim 64 with _SINGLE_PASS_MIN_NK <= Nk <= 256 and 16-byte-aligned
+# rows, with or without a mask: it was measured faster than the two-pass
+# kernels without a mask at Nk = 49, 64, 144 and 197, and with one ([1,H,N,N]
+# bias, cyclic [mB,H,N,N] bias + shift mask) at Nk = 49, 64, 100, 144 and 197
+# (smallest margin: 28 us of 380 at Nk = 64 with a bias).  Everything else -
+# longer sequences, other head dims, and Nk < 49, which was not measured -
+# stays on the two-pass kernels.  Where no bias gradient is wanted the single-pass
+# kernel reads dO and O through their strides and forms delta itself, so
+# attn_bwd_preprocess is not launched; with a bias gradient the preprocess
+# still runs, because the dBias kernel needs its contiguous dO and delta.
+_SINGLE_PASS_MAX_NK = 256
+_SINGLE_PASS_MIN_NK = 49
+_BWD_PATHS = ('two_pass', 'single_pass', 'single_pass_preprocess')
+_BWD_PATH_FORCED: Optional[str] = None
+# calls per path since import: lets a test assert which kernels ran
+BWD_PATH_CALLS = {'two_pass': 0, 'single_pass': 0}
+
+
+def set_attn_bwd_path(path: Optional[str] = None):
+    """Force the fused backward: 'two_pass', 'single_pass' (wherever the
+    single-pass kernel supports the shape) or 'single_pass_preprocess' (the
+    same kernel fed by attn_bwd_preprocess, for tools/bench_attn_bwd.py);
+    None goes back to the measured rule.  TIMM_AMD_ATTN_BWD=two_pass sets the
+    first of these for a whole process."""
+    global _BWD_PATH_FORCED
+    assert path is None or path in _BWD_PATHS, path
+    _BWD_PATH_FORCED = path
+
+
+def _aligned16(t):
+    return (t.dim() == 4 and t.stride(-1) == 1 and t.data_ptr() % 16 == 0
+            and all(s % 8 == 0 for s in t.stride()[:3]))
+
+
+def _single_pass_supported(q, k, v, dq, dk, dv):
+    return (q.shape[-1] == 64 and 1 <= k.shape[2] <= _SINGLE_PASS_MAX_NK
+            and q.numel() > 0 and all(_aligned16(t) for t in (q, k, v, dq, dk, dv)))
+
+
+def _select_bwd_path(q, k, v, dq, dk, dv) -> str:
+    forced = _BWD_PATH_FORCED
+    if forced is None and _BWD_MODE == 'two_pass':
+        forced = 'two_pass'
+    if forced == 'two_pass' or not _single_pass_supported(q, k, v, dq, dk, dv):
+        return 'two_pass'
+    if forced is not None:
+        return forced
+    return 'single_pass' if k.shape[2] >= _SINGLE_PASS_MIN_NK else 'two_pass'
+
+
 def _fused_backward(ext, q, k, v, o, lse, do, attn_mask, scale, dq, dk, dv, need_dbias=False):
     """Shared fused-backward driver writing into preallocated dq/dk/dv.
     Returns the fp32 mask gradient when `need_dbias`, else None."""
+    path = _select_bwd_path(q, k, v, dq, dk, dv)
+    if path == 'single_pass' and not need_dbias:
+        BWD_PATH_CALLS['single_pass'] += 1
+        if not _aligned16(do):
+            do = do.contiguous()
+        ext.attention_bwd_single_pass(
+            q, k, v, do, o, lse, None, attn_mask, dq, dk, dv, scale)
+        return None
     if do.dim() == 4 and do.stride(-1) == 1 and do.shape[-1] % 32 == 0 and do.shape[-1] <= 128:
         do_c, delta = ext.attn_bwd_preprocess(do, o)
     else:
         do_c = do.contiguous()
         delta = (do_c * o).float().sum(-1)
-    ext.attention_bwd(q, k, v, do_c, lse, delta, attn_mask, dq, dk, dv, scale)
+    if path == 'two_pass':
+        BWD_PATH_CALLS['two_pass'] += 1
+        ext.attention_bwd(q, k, v, do_c, lse, delta, attn_mask, dq, dk, dv, scale)
+    else:
+        BWD_PATH_CALLS['single_pass'] += 1
+        ext.attention_bwd_single_pass(
+            q, k, v, do_c, None, lse, delta, attn_mask, dq, dk, dv, scale)
     if need_dbias:
         return ext.attention_bwd_dbias(
             q, k, v, do_c, lse, delta, attn_mask, scale, _mask_nsplit(q, k, attn_mask))
@@ -235,6 +314,14 @@ class _FlashAttnQkvFn(torch.autograd.Function):
         dk = dqkv[:, :, 1].permute(0, 2, 1, 3)
         dv = dqkv[:, :, 2].permute(0, 2, 1, 3)
         need_dbias = ctx.attn_mask is not None and ctx.needs_input_grad[1]
+        if _BWD_MODE == 'gemm':
+            # the A/B reference path reaches the packed entry too (the ViT blocks)
+            gq, gk, gv, dbias = _gemm_backward(
+                ext, q, k, v, o, lse, do, ctx.attn_mask, ctx.scale, need_dbias)
+            dq.copy_(gq)
+            dk.copy_(gk)
+            dv.copy_(gv)
+            return dqkv, dbias, None
         dbias = _fused_backward(
             ext, q, k, v, o, lse, do, ctx.attn_mask, ctx.scale, dq, dk, dv, need_dbias)
         return dqkv, dbias, None

@@ -1,4 +1,12 @@
-// Fused flash-style attention BACKWARD for gfx950 (CDNA4).
+// Fused flash-style attention BACKWARD for gfx950 (CDNA4): the two-pass
+// kernels and the dBias pass.
+//
+// Which backward runs when (dispatch in timm_amd/ops/attention.py): head_dim
+// 64 with 49 <= Nk <= 256 goes to the single-pass kernel in
+// attention_bwd_single_pass.hip (one workgroup per (batch, head) owns every
+// key).  The two passes below serve everything else: Nk > 256, head dims 32 /
+// 96 / 128, key counts under 49, unaligned rows, and TIMM_AMD_ATTN_BWD=two_pass.
+// The dBias pass serves both.
 //
 // Replaces the round-1 GEMM-recompute backward (which materialized S, P, dP,
 // dS as [B,H,Nq,Nk] bf16 tensors in HBM via hipBLASLt).  Reference semantics:

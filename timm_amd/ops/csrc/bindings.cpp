@@ -37,6 +37,14 @@ at::Tensor attention_bwd_dbias(at::Tensor q, at::Tensor k, at::Tensor v,
                                at::Tensor dov, at::Tensor lse, at::Tensor delta,
                                at::Tensor mask, double scale, int64_t nsplit);
 
+// attention_bwd_single_pass.hip
+void attention_bwd_single_pass(at::Tensor q, at::Tensor k, at::Tensor v,
+                               at::Tensor dov, c10::optional<at::Tensor> o,
+                               at::Tensor lse, c10::optional<at::Tensor> delta,
+                               c10::optional<at::Tensor> mask,
+                               at::Tensor dq, at::Tensor dk, at::Tensor dv,
+                               double scale);
+
 // depthwise_conv.hip
 at::Tensor dwconv_fwd(at::Tensor x, at::Tensor w_t, c10::optional<at::Tensor> bias,
                       long stride, long pad, long K, long Ho, long Wo);
@@ -97,6 +105,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "fused flash attention bwd: gradient of the additive mask/bias (MFMA, gfx950)",
         py::arg("q"), py::arg("k"), py::arg("v"), py::arg("dov"), py::arg("lse"),
         py::arg("delta"), py::arg("mask"), py::arg("scale"), py::arg("nsplit") = 1);
+  m.def("attention_bwd_single_pass", &attention_bwd_single_pass,
+        "single-pass fused attention bwd, Nk <= 256, head_dim 64 (MFMA, gfx950)");
   m.def("dwconv_fwd", &dwconv_fwd, "NHWC depthwise conv fwd (gfx950)");
   m.def("dwconv_bwd_data", &dwconv_bwd_data, "NHWC depthwise conv bwd-data");
   m.def("dwconv_bwd_weight", &dwconv_bwd_weight, "NHWC depthwise conv bwd-weight");
