@@ -3,7 +3,10 @@ parametrized forward/backward over the registry with tiny inputs, default-cfg
 invariants (forward_features unpooled shape, reset_classifier, global_pool='').
 CPU-only; GPU parity lives in test_ops_gpu.py.
 """
+import fcntl
 import fnmatch
+import os
+import tempfile
 
 import pytest
 import torch
@@ -62,10 +65,29 @@ def _models(filters='', exclude=()):
     return list_models(filter=filters, exclude_filters=list(EXCLUDE_FILTERS) + list(exclude))
 
 
+# ~1.8B-parameter towers: one fp32 forward+backward holds 16-20 GB of host
+# memory. Their names sort next to each other, so the xdist workers reach them
+# in the same minute and together can exceed a 64 GB host; one runs at a time.
+SERIAL_FILTERS = ['*gigantic*']
+
+
+@pytest.fixture
+def one_at_a_time(request):
+    """Hold a host-wide lock for the whole test of a SERIAL_FILTERS model."""
+    model_name = request.node.callspec.params['model_name']
+    if not any(fnmatch.fnmatch(model_name, f) for f in SERIAL_FILTERS):
+        yield
+        return
+    path = os.path.join(tempfile.gettempdir(), f'timm_amd_test_models_{os.getuid()}.lock')
+    with open(path, 'w') as f:
+        fcntl.flock(f, fcntl.LOCK_EX)  # released when f closes
+        yield
+
+
 @pytest.mark.base
 @pytest.mark.parametrize('model_name', _models())
 @pytest.mark.parametrize('batch_size', [1])
-def test_model_forward(model_name, batch_size):
+def test_model_forward(model_name, batch_size, one_at_a_time):
     """Run a single forward pass with each model."""
     model = create_model(model_name, pretrained=False, num_classes=10)
     model.eval()
@@ -82,7 +104,7 @@ def test_model_forward(model_name, batch_size):
 @pytest.mark.base
 @pytest.mark.parametrize('model_name', _models(exclude=['*_384*', '*_448*', '*_512*']))
 @pytest.mark.parametrize('batch_size', [2])
-def test_model_backward(model_name, batch_size):
+def test_model_backward(model_name, batch_size, one_at_a_time):
     """Run a single forward + backward pass with each model."""
     # fixed-input-size models above MAX_BWD_SIZE run at their own size
     input_size = _get_input_size(model_name=model_name, target=TARGET_BWD_SIZE)
