@@ -6,7 +6,8 @@ hand-written CDNA4 (gfx950) HIP kernel compiled into the in-tree extension
 `timm_amd._C`:
 
  * layer_norm / rms_norm (+LayerScale fusion)          — one read of x, two-pass fp32 statistics
- * attention (flash-style fused SDPA, bf16/fp16)       — MFMA 16x16x32, online softmax
+ * attention (flash-style fused SDPA, bf16)            — MFMA 16x16x32, online softmax;
+   any head_dim % 8 == 0 up to 128 (72 / 80 / 88 / 104 / 48 included), fwd + bwd
  * attention bias gradient (learned rel-pos bias)      — flash dBias pass, fp32, no atomics
  * bias_act (bias+GELU/SiLU epilogue after GEMM)
  * residual add (+ LayerScale + DropPath) epilogue

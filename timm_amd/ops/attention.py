@@ -21,6 +21,14 @@ directions are hand-written flash-style gfx950 HIP kernels:
        is wanted.
      - two-pass (attn_bwd_dq / attn_bwd_dkdv kernels behind
        attn_bwd_preprocess): everything else — Nk > 256, other head dims.
+ * head dims: bf16 with head_dim % 8 == 0, 8 <= head_dim <= 128.  Multiples
+   of 32 run the kernels above.  Every other one (72: so400m SigLIP ViTs,
+   80: ViT-H / SAM-H, 88: ViT-g / EVA-giant, 104: ViT-gigantic, 48: CaiT /
+   ConViT, 40 / 24 / 16 / 8) runs the kernels of csrc/attention_head_dims.hip
+   behind the same entries: forward, preprocess, two-pass dQ and dK/dV, and
+   dBias, on LDS rows padded to round_up(D, 16) + 8 elements with a 16-wide
+   MFMA tail step, reading q/k/v in place (packed qkv views included) - no
+   padded copy and no [B,H,Nq,Nk] tensor in HBM for these either.
    TIMM_AMD_ATTN_BWD=two_pass forces the two-pass kernels for a process,
    `set_attn_bwd_path` forces either from code; the round-1 hipBLASLt
    GEMM-recompute chain remains available via TIMM_AMD_ATTN_BWD=gemm for A/B
@@ -57,8 +65,13 @@ _BWD_MODE = os.environ.get('TIMM_AMD_ATTN_BWD', 'fused')
 def attention_available(q: torch.Tensor) -> bool:
     if not q.is_cuda or _load_extension() is None:
         return False
-    D = q.shape[-1]
-    return D <= 128 and D % 32 == 0 and q.dtype == torch.bfloat16
+    return _head_dim_ok(q.shape[-1]) and q.dtype == torch.bfloat16
+
+
+def _head_dim_ok(D: int) -> bool:
+    # multiples of 32: attention.hip / attention_bwd*.hip; the other multiples
+    # of 8 (72, 80, 88, 104, 48, ...): attention_head_dims.hip
+    return 8 <= D <= 128 and D % 8 == 0
 
 
 def _cyclic_mask(attn_mask, B):
@@ -81,7 +94,10 @@ def _math_sdpa(q, k, v, attn_mask=None, scale=None):
 
 
 def _strides_ok(t):
-    return t.stride(-1) == 1 and all(s % 8 == 0 or s == 0 for s in t.stride()[:3])
+    # 16-byte chunks through the tensor's own strides (the launchers for head
+    # dims that are no multiple of 32 check this and refuse anything else)
+    return (t.stride(-1) == 1 and t.data_ptr() % 16 == 0
+            and all(s % 8 == 0 for s in t.stride()[:3]))
 
 
 def _prep_mask(attn_mask, q, k):
@@ -194,6 +210,15 @@ def _select_bwd_path(q, k, v, dq, dk, dv) -> str:
     return 'single_pass' if k.shape[2] >= _SINGLE_PASS_MIN_NK else 'two_pass'
 
 
+def _preprocess_ok(do):
+    """attn_bwd_preprocess reads dO through its strides in 16-byte chunks; the
+    kernels for head dims that are no multiple of 32 check the alignment."""
+    D = do.shape[-1]
+    if do.dim() != 4 or do.stride(-1) != 1 or not _head_dim_ok(D):
+        return False
+    return D % 32 == 0 or _aligned16(do)
+
+
 def _fused_backward(ext, q, k, v, o, lse, do, attn_mask, scale, dq, dk, dv, need_dbias=False):
     """Shared fused-backward driver writing into preallocated dq/dk/dv.
     Returns the fp32 mask gradient when `need_dbias`, else None."""
@@ -205,7 +230,7 @@ def _fused_backward(ext, q, k, v, o, lse, do, attn_mask, scale, dq, dk, dv, need
         ext.attention_bwd_single_pass(
             q, k, v, do, o, lse, None, attn_mask, dq, dk, dv, scale)
         return None
-    if do.dim() == 4 and do.stride(-1) == 1 and do.shape[-1] % 32 == 0 and do.shape[-1] <= 128:
+    if _preprocess_ok(do):
         do_c, delta = ext.attn_bwd_preprocess(do, o)
     else:
         do_c = do.contiguous()
@@ -226,7 +251,7 @@ def _fused_backward(ext, q, k, v, o, lse, do, attn_mask, scale, dq, dk, dv, need
 def _gemm_backward(ext, q, k, v, o, lse, do, attn_mask, scale, need_dbias=False):
     """Round-1 exact recompute via hipBLASLt GEMMs (A/B reference path).
     The mask gradient comes from the same dBias kernel as the fused path."""
-    if do.dim() == 4 and do.stride(-1) == 1 and do.shape[-1] % 32 == 0 and do.shape[-1] <= 128:
+    if _preprocess_ok(do):
         do, delta = ext.attn_bwd_preprocess(do, o)
     else:
         do = do.contiguous()

@@ -5,7 +5,7 @@
 //
 // Structure (correctness-first v1, per the CDNA4 guide's fused-attn anatomy):
 //  * 256-thread block = 4 waves; each block owns a 64-row Q tile of one (b,h)
-//  * K/V staged in LDS in 32-row tiles; Q staged once per block
+//  * K/V staged in LDS in 64-row tiles; Q staged once per block
 //  * QK^T and PV on MFMA v_mfma_f32_16x16x32_bf16 (per-wave 16x16 tiles)
 //  * online softmax with fp32 running max/sum state per q-row
 //    (C/D fragment layout: row=(lane>>4)*4+reg, col=lane&15 — all lanes of a
@@ -13,10 +13,13 @@
 //  * optional additive fp32 mask [B,1,Nq,Nk] (NaFlex padding masks)
 //  * returns O (bf16) + logsumexp (fp32) for the exact GEMM-based backward
 //
-// Supported: dtype bf16, head_dim in {32,64,96,128}, any Nq/Nk.
+// Supported: dtype bf16, any Nq/Nk; head_dim in {32,64,96,128} here, every
+// other head_dim % 8 == 0 up to 128 in attention_head_dims.hip (the host
+// entries below dispatch).
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 #include "common.h"
+#include "attention_head_dims.h"
 
 namespace {
 
@@ -34,7 +37,7 @@ __device__ __forceinline__ int swz(int row, int byte_off) {
   return kSwz ? (byte_off ^ ((row & 7) << 4)) : byte_off;
 }
 
-// swizzle for 64-byte LDS rows (transposed V tile over the 32-row kv dim)
+// swizzle for the 128-byte LDS rows of the transposed V tile (64 kv rows)
 template <bool kSwz>
 __device__ __forceinline__ int swz64(int row, int byte_off) {
   return kSwz ? (byte_off ^ ((row & 3) << 4)) : byte_off;
@@ -56,10 +59,10 @@ void attn_fwd_kernel(
     long q_sb, long q_sh, long q_sn,
     long k_sb, long k_sh, long k_sn,
     long v_sb, long v_sh, long v_sn) {
-  // LDS: Q[64][D] | K[32][D] | V[32][D] | P[4][16][32]
+  // LDS: Q[64][D] | K[64][D] | V^T[D][64] | P[4][16][64]
   __shared__ __bf16 q_lds[kQTile * kMaxD];
   __shared__ __bf16 k_lds[kKvTile * kMaxD];
-  __shared__ __bf16 vt_lds[kMaxD * kKvTile];  // V transposed: [d][kv], 64B rows
+  __shared__ __bf16 vt_lds[kMaxD * kKvTile];  // V transposed: [d][kv], 128B rows
   __shared__ __bf16 p_lds[4 * 16 * kKvTile];
 
   const int bh = blockIdx.y;
@@ -406,7 +409,8 @@ std::vector<at::Tensor> attention_fwd(at::Tensor q, at::Tensor k, at::Tensor v,
   TORCH_CHECK(q.dim() == 4);
   int B = q.size(0), H = q.size(1), Nq = q.size(2), D = q.size(3);
   int Nk = k.size(2);
-  TORCH_CHECK(D % 32 == 0 && D <= 128, "attention_fwd: head_dim must be multiple of 32, <=128");
+  TORCH_CHECK(D % 8 == 0 && D >= 8 && D <= 128,
+              "attention_fwd: head_dim must be a multiple of 8, <=128");
   if (mask.has_value()) {
     TORCH_CHECK(mask->is_contiguous() && mask->scalar_type() == at::kFloat);
     TORCH_CHECK(mask->size(0) >= 1 && B % mask->size(0) == 0 &&
@@ -414,6 +418,7 @@ std::vector<at::Tensor> attention_fwd(at::Tensor q, at::Tensor k, at::Tensor v,
                 mask->size(2) == Nq && mask->size(3) == Nk,
                 "attention_fwd: mask must be [mB|1,H|1,Nq,Nk] with mB dividing B");
   }
+  if (D % 32 != 0) return attention_fwd_head_dims(q, k, v, mask, scale);
   // O allocated [B, Nq, H, D] and returned as a permuted [B,H,Nq,D] view so
   // the caller's transpose(1,2).reshape(B,N,C) is a zero-copy reshape.
   auto o_bnhd = at::empty({B, Nq, H, D}, q.options());
@@ -482,7 +487,8 @@ std::vector<at::Tensor> attn_bwd_preprocess(at::Tensor dout, at::Tensor o) {
   TORCH_CHECK(dout.is_cuda() && dout.dim() == 4 && dout.scalar_type() == at::kBFloat16);
   TORCH_CHECK(dout.stride(3) == 1 && o.stride(3) == 1, "head_dim must be contiguous");
   int B = dout.size(0), H = dout.size(1), N = dout.size(2), D = dout.size(3);
-  TORCH_CHECK(D % 32 == 0 && D <= 128);
+  TORCH_CHECK(D % 8 == 0 && D >= 8 && D <= 128);
+  if (D % 32 != 0) return attn_bwd_preprocess_head_dims(dout, o);
   auto do_c = at::empty({B, H, N, D}, dout.options());
   auto delta = at::empty({B, H, N}, dout.options().dtype(at::kFloat));
   long rows = (long)B * H * N;

@@ -6,7 +6,10 @@
 // attention_bwd_single_pass.hip (one workgroup per (batch, head) owns every
 // key).  The two passes below serve everything else: Nk > 256, head dims 32 /
 // 96 / 128, key counts under 49, unaligned rows, and TIMM_AMD_ATTN_BWD=two_pass.
-// The dBias pass serves both.
+// The dBias pass serves both.  Head dims that are no multiple of 32 (any
+// D % 8 == 0 up to 128: 72, 80, 88, 104, 48, ...) always take the two-pass
+// route with the kernels of attention_head_dims.hip; attention_bwd and
+// attention_bwd_dbias below validate and dispatch.
 //
 // Replaces the round-1 GEMM-recompute backward (which materialized S, P, dP,
 // dS as [B,H,Nq,Nk] bf16 tensors in HBM via hipBLASLt).  Reference semantics:
@@ -37,6 +40,7 @@
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 #include "common.h"
+#include "attention_head_dims.h"
 
 namespace {
 
@@ -695,11 +699,16 @@ void attention_bwd(at::Tensor q, at::Tensor k, at::Tensor v,
   TORCH_CHECK(dov.is_contiguous(), "attention_bwd: dO must be contiguous");
   int B = q.size(0), H = q.size(1), Nq = q.size(2), D = q.size(3);
   int Nk = k.size(2);
-  TORCH_CHECK(D % 32 == 0 && D <= 128, "attention_bwd: head_dim multiple of 32, <=128");
+  TORCH_CHECK(D % 8 == 0 && D >= 8 && D <= 128,
+              "attention_bwd: head_dim must be a multiple of 8, <=128");
   if (mask.has_value()) {
     TORCH_CHECK(mask->is_contiguous() && mask->scalar_type() == at::kFloat);
     TORCH_CHECK(B % mask->size(0) == 0 && (mask->size(1) == H || mask->size(1) == 1) &&
                 mask->size(2) == Nq && mask->size(3) == Nk);
+  }
+  if (D % 32 != 0) {
+    attention_bwd_head_dims(q, k, v, dov, lse, delta, mask, dq, dk, dv, scale);
+    return;
   }
   auto stream = at::hip::getCurrentHIPStream();
   if (D <= 32) {
@@ -734,7 +743,8 @@ at::Tensor attention_bwd_dbias(at::Tensor q, at::Tensor k, at::Tensor v,
   TORCH_CHECK(dov.is_contiguous(), "attention_bwd_dbias: dO must be contiguous");
   int B = q.size(0), H = q.size(1), Nq = q.size(2), D = q.size(3);
   int Nk = k.size(2);
-  TORCH_CHECK(D % 32 == 0 && D <= 128, "attention_bwd_dbias: head_dim multiple of 32, <=128");
+  TORCH_CHECK(D % 8 == 0 && D >= 8 && D <= 128,
+              "attention_bwd_dbias: head_dim must be a multiple of 8, <=128");
   TORCH_CHECK(k.size(0) == B && k.size(1) == H && k.size(3) == D &&
               v.size(0) == B && v.size(1) == H && v.size(2) == Nk && v.size(3) == D &&
               dov.sizes() == q.sizes(), "attention_bwd_dbias: q/k/v/dO shapes disagree");
@@ -761,7 +771,9 @@ at::Tensor attention_bwd_dbias(at::Tensor q, at::Tensor k, at::Tensor v,
     out = slabs.data_ptr<float>();
   }
   auto stream = at::hip::getCurrentHIPStream();
-  if (D <= 32) {
+  if (D % 32 != 0) {
+    attention_bwd_dbias_head_dims(q, k, v, dov, lse, delta, mask, out, scale, n_red, chunk, ns);
+  } else if (D <= 32) {
     launch_attn_bwd_dbias<32>(q, k, v, dov, lse, delta, mask, out, H, Nq, Nk, D,
                               (float)scale, n_red, chunk, ns, stream);
   } else if (D <= 64) {
