@@ -13,7 +13,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ..data.constants import IMAGENET_DEFAULT_MEAN, IMAGENET_DEFAULT_STD
-from ..ops import flash_attention
+from ..ops import flash_attention, window_attention
 from ..ops.attention import attention_available
 from ..layers import (
     ClassifierHead, DropPath, Mlp, PatchEmbed, _assert, calculate_drop_path_rates, get_norm_layer,
@@ -271,8 +271,27 @@ class SwinTransformerBlock(nn.Module):
             persistent=False,
         )
 
+    def _map_attn_ok(self, x) -> bool:
+        """Whether the windowed-attention kernels can read this map in place."""
+        attn = self.attn
+        H, W = x.shape[1], x.shape[2]
+        if not (attn.fused_attn and attn.attn_drop.p == 0. and attn.head_dim == 32
+                and self.window_area <= 64
+                and H % self.window_size[0] == 0 and W % self.window_size[1] == 0):
+            return False
+        return x.dtype == torch.bfloat16 and attention_available(
+            x.new_empty((1, attn.num_heads, 1, attn.head_dim)))
+
     def _attn(self, x):
         B, H, W, C = x.shape
+
+        if self._map_attn_ok(x):
+            # shift, partition, reverse and the shift mask are addressing
+            # inside the kernels: qkv runs on the map as it is
+            x = window_attention(
+                self.attn.qkv(x), self.attn.num_heads, self.window_size, self.shift_size,
+                bias=self.attn._get_rel_pos_bias()[0], scale=self.attn.scale)
+            return self.attn.proj_drop(self.attn.proj(x))
 
         # cyclic shift
         has_shift = any(self.shift_size)

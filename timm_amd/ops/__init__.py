@@ -9,6 +9,8 @@ hand-written CDNA4 (gfx950) HIP kernel compiled into the in-tree extension
  * attention (flash-style fused SDPA, bf16)            — MFMA 16x16x32, online softmax;
    any head_dim % 8 == 0 up to 128 (72 / 80 / 88 / 104 / 48 included), fwd + bwd
  * attention bias gradient (learned rel-pos bias)      — flash dBias pass, fp32, no atomics
+ * window_attention (Swin W-MSA / SW-MSA on the map)   — shift, partition, reverse and shift mask
+   as addressing; one wave per (window, head), single-pass bwd with dBias (head_dim 32, N <= 64)
  * bias_act (bias+GELU/SiLU epilogue after GEMM)
  * residual add (+ LayerScale + DropPath) epilogue
  * multi-tensor fused optimizer steps (AdamW/LAMB/SGD/lerp-EMA)
@@ -73,6 +75,7 @@ def use_hip(x: torch.Tensor) -> bool:
 from .conv import depthwise_conv2d  # noqa: E402
 from .layer_norm import layer_norm_act, rms_norm_act, layer_norm, rms_norm  # noqa: E402
 from .attention import flash_attention, flash_attention_qkv, attention_available  # noqa: E402
+from .window_attention import window_attention  # noqa: E402
 from .elementwise import bias_act, residual_scale_add  # noqa: E402
 from .fused_optim import fused_adamw_step, fused_lamb_step, fused_lerp_, fused_l2norm  # noqa: E402
 from .loss import fused_cross_entropy  # noqa: E402
@@ -83,7 +86,7 @@ __all__ = [
     'has_ext', 'require_ext', 'use_hip',
     'depthwise_conv2d',
     'layer_norm', 'layer_norm_act', 'rms_norm', 'rms_norm_act',
-    'flash_attention', 'flash_attention_qkv', 'attention_available',
+    'flash_attention', 'flash_attention_qkv', 'attention_available', 'window_attention',
     'bias_act', 'residual_scale_add',
     'fused_adamw_step', 'fused_lamb_step', 'fused_lerp_', 'fused_l2norm',
     'fused_cross_entropy', 'u8_normalize', 'masked_global_pool',
