@@ -21,6 +21,7 @@ sources = [
     os.path.join(CSRC, 'attention_bwd.hip'),
     os.path.join(CSRC, 'attention_bwd_single_pass.hip'),
     os.path.join(CSRC, 'attention_head_dims.hip'),
+    os.path.join(CSRC, 'attention_key_mask.hip'),
     os.path.join(CSRC, 'window_attention.hip'),
     os.path.join(CSRC, 'depthwise_conv.hip'),
     os.path.join(CSRC, 'multi_tensor.hip'),

@@ -25,6 +25,7 @@ from ..data.constants import IMAGENET_DEFAULT_MEAN, IMAGENET_DEFAULT_STD, OPENAI
 from ..layers import (
     AttentionPoolLatent, LayerNorm, Mlp, PatchDropout, RmsNorm, RotaryEmbeddingCat,
     calculate_drop_path_rates, get_act_layer, get_norm_layer, to_2tuple, trunc_normal_,
+    use_fused_attn,
 )
 from ._builder import build_model_with_cfg
 from ._features import feature_take_indices
@@ -439,14 +440,32 @@ class NaFlexVit(nn.Module):
             patch_valid = None
         return patches, patch_coord, patch_valid, grid
 
+    def _block_attn_mask(self, patch_valid: Optional[torch.Tensor], h: torch.Tensor):
+        """The padding mask the blocks get: None without `patch_valid`."""
+        if patch_valid is None:
+            return None
+        if (h.is_cuda and use_fused_attn()
+                and all(getattr(blk.attn, 'fused_attn', False) for blk in self.blocks)):
+            # Key-padding form, bool [B,1,1,N] (prefix tokens valid): the fused
+            # attention op runs its key-mask kernels on it, no [B,1,N,N] fp32
+            # tensor is built.  Only keys are masked, so a padded query row now
+            # attends to the valid keys and is no longer zero.  Padded keys are
+            # masked in every block and the pooling is masked, so the valid
+            # rows and the logits are the same function as with the symmetric
+            # mask, and the loss gives padded rows a zero gradient.
+            key_valid = patch_valid.bool()
+            if self.num_prefix_tokens:
+                prefix = key_valid.new_ones(key_valid.shape[0], self.num_prefix_tokens)
+                key_valid = torch.cat([prefix, key_valid], dim=1)
+            return key_valid[:, None, None, :]
+        return create_attention_mask(
+            patch_valid, num_prefix_tokens=self.num_prefix_tokens, dtype=torch.float32)
+
     def forward_features(self, x) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
         patches, patch_coord, patch_valid, _ = self._unpack(x)
         h = self.embeds(patches, patch_coord=patch_coord, patch_valid=patch_valid)
 
-        attn_mask = None
-        if patch_valid is not None:
-            attn_mask = create_attention_mask(
-                patch_valid, num_prefix_tokens=self.num_prefix_tokens, dtype=torch.float32)
+        attn_mask = self._block_attn_mask(patch_valid, h)
 
         rope_embed = None
         if self.rope is not None:
@@ -500,10 +519,7 @@ class NaFlexVit(nn.Module):
         take_indices, max_index = feature_take_indices(len(self.blocks), indices)
         patches, patch_coord, patch_valid, _ = self._unpack(x)
         h = self.embeds(patches, patch_coord=patch_coord, patch_valid=patch_valid)
-        attn_mask = None
-        if patch_valid is not None:
-            attn_mask = create_attention_mask(
-                patch_valid, num_prefix_tokens=self.num_prefix_tokens, dtype=torch.float32)
+        attn_mask = self._block_attn_mask(patch_valid, h)
         intermediates = []
         blocks = self.blocks if not stop_early else self.blocks[:max_index + 1]
         for i, blk in enumerate(blocks):

@@ -9,6 +9,9 @@ hand-written CDNA4 (gfx950) HIP kernel compiled into the in-tree extension
  * attention (flash-style fused SDPA, bf16)            — MFMA 16x16x32, online softmax;
    any head_dim % 8 == 0 up to 128 (72 / 80 / 88 / 104 / 48 included), fwd + bwd
  * attention bias gradient (learned rel-pos bias)      — flash dBias pass, fp32, no atomics
+ * key-padding attention (bool [B,1,1,Nk] attn_mask)   — validity as bits in scalar registers,
+   all-padding key tiles skipped before their loads, fwd + bwd (head_dim 64); bool masks
+   mean "True takes part" on every attention path
  * window_attention (Swin W-MSA / SW-MSA on the map)   — shift, partition, reverse and shift mask
    as addressing; one wave per (window, head), single-pass bwd with dBias (head_dim 32, N <= 64)
  * bias_act (bias+GELU/SiLU epilogue after GEMM)

@@ -43,6 +43,16 @@ directions are hand-written flash-style gfx950 HIP kernels:
    inference) cost no extra launch or allocation.  Broadcast shapes are
    reduced by autograd through `_prep_mask`, which stays outside the
    autograd Function.
+ * bool masks: True = the key takes part (F.scaled_dot_product_attention
+   semantics) on every path; a query row with no valid key gives zeros and
+   zero gradients.  A bool [B,1,1,Nk] mask is a key-padding mask (NaFlex):
+   at bf16, head_dim 64 it runs the kernels of csrc/attention_key_mask.hip,
+   which take the validity as uint8 [B,Nk], hold it as one 64-bit word per
+   64-key tile in scalar registers, skip tiles with no valid key before any
+   K/V load and write exact zeros to dk / dv of padded keys - no [B,1,N,N]
+   fp32 tensor is built or read.  KEY_MASK_CALLS counts their calls.  Every
+   other bool mask (other shapes, head dims, dtypes, Nk > 4096) becomes the
+   additive fp32 mask (finfo.min at False) of the kernels above.
  * flash_attention_qkv: packed-qkv entry — takes the [B,N,3,H,D] projection
    output directly and writes gradients into one packed dqkv buffer, so the
    qkv-unbind `aten::copy_`/stack grad chain never appears in the graph.
@@ -82,13 +92,27 @@ def _cyclic_mask(attn_mask, B):
     return attn_mask
 
 
+def _masked_softmax(attn, attn_mask, B):
+    """softmax(attn + mask) for a float mask; for a bool mask (True = the key
+    takes part) softmax over the True entries, a row with none giving zeros."""
+    if attn_mask is None:
+        return attn.softmax(dim=-1)
+    attn_mask = _cyclic_mask(attn_mask, B)
+    if attn_mask.dtype != torch.bool:
+        return (attn + attn_mask).softmax(dim=-1)
+    # the -inf rows come out of softmax as NaN; both masked_fills give those
+    # entries a zero gradient, so nothing of it reaches q, k or v
+    attn = attn.masked_fill(~attn_mask, float('-inf')).softmax(dim=-1)
+    return attn.masked_fill(~attn_mask.any(dim=-1, keepdim=True), 0.)
+
+
 def _math_sdpa(q, k, v, attn_mask=None, scale=None):
     """Reference composition (matches F.scaled_dot_product_attention semantics)."""
     scale = scale if scale is not None else 1.0 / math.sqrt(q.shape[-1])
     attn = (q.float() @ k.float().transpose(-2, -1)) * scale
-    if attn_mask is not None:
-        attn = attn + _cyclic_mask(attn_mask, q.shape[0]).float()
-    attn = attn.softmax(dim=-1)
+    if attn_mask is not None and attn_mask.dtype != torch.bool:
+        attn_mask = attn_mask.float()
+    attn = _masked_softmax(attn, attn_mask, q.shape[0])
     out = attn @ v.float()
     return out.to(q.dtype)
 
@@ -172,6 +196,24 @@ def _mask_nsplit(q, k, attn_mask) -> int:
 # still runs, because the dBias kernel needs its contiguous dO and delta.
 _SINGLE_PASS_MAX_NK = 256
 _SINGLE_PASS_MIN_NK = 49
+# Key-padding masks (bool [B,1,1,Nk], bf16, head_dim 64, no dropout) run the
+# kernels of csrc/attention_key_mask.hip for _KEY_MASK_MIN_NK <= Nk <=
+# _KEY_MASK_MAX_NK (the kernels keep one validity word per 64 keys in a
+# 64-word LDS array).  Outside that range, and for every other bool mask, the
+# mask is turned into the additive fp32 form and takes the rule above.
+# Numbers: profiles/attn_key_mask/README.md.  Against the additive [B,1,N,N]
+# mask on packed 12-head qkv the key-mask kernels were faster forward and
+# forward+backward at Nk = 32, 64, 128, 256, 576 and 1024, also where the
+# additive path runs the single-pass backward (forward+backward 256 us against
+# 342 at Nk = 64, 321 against 367 at 128, 500 against 622 at 256, the
+# smallest margin; 974 against 2072 at 576), so there is no lower bound.  They
+# are a two-pass pair behind attn_bwd_preprocess; set_attn_bwd_path and
+# TIMM_AMD_ATTN_BWD=two_pass do not apply to them, TIMM_AMD_ATTN_BWD=gemm
+# takes the additive form.
+_KEY_MASK_MIN_NK = 1
+_KEY_MASK_MAX_NK = 4096
+# calls of the key-mask kernels since import: lets a test assert that they ran
+KEY_MASK_CALLS = {'fwd': 0, 'bwd': 0}
 _BWD_PATHS = ('two_pass', 'single_pass', 'single_pass_preprocess')
 _BWD_PATH_FORCED: Optional[str] = None
 # calls per path since import: lets a test assert which kernels ran
@@ -352,6 +394,83 @@ class _FlashAttnQkvFn(torch.autograd.Function):
         return dqkv, dbias, None
 
 
+def _bool_to_additive(attn_mask):
+    """Bool mask (True = the key takes part) as the additive fp32 mask of the
+    existing kernels: finfo.min at the False entries, which they clamp, so a
+    row with no True entry gives O = 0 and zero gradients."""
+    out = torch.zeros(attn_mask.shape, dtype=torch.float32, device=attn_mask.device)
+    return out.masked_fill_(~attn_mask, torch.finfo(torch.float32).min)
+
+
+def _key_valid(attn_mask, q, k, v):
+    """The uint8 [B,Nk] validity vector when the key-mask kernels serve this
+    call (q/k/v already known to be on the GPU in bf16), else None."""
+    B, Nk = q.shape[0], k.shape[2]
+    if (attn_mask.dtype != torch.bool or tuple(attn_mask.shape) != (B, 1, 1, Nk)
+            or _BWD_MODE == 'gemm' or not _KEY_MASK_MIN_NK <= Nk <= _KEY_MASK_MAX_NK
+            or q.numel() == 0 or q.shape[1] * B > 65535
+            or not all(t.shape[-1] == 64 and _aligned16(t) for t in (q, k, v))):
+        return None
+    return attn_mask.reshape(B, Nk).to(torch.uint8)
+
+
+def _key_mask_backward(ext, q, k, v, o, lse, do, valid, scale, dq, dk, dv):
+    if _preprocess_ok(do):
+        do_c, delta = ext.attn_bwd_preprocess(do, o)
+    else:
+        do_c = do.contiguous()
+        delta = (do_c * o).float().sum(-1)
+    KEY_MASK_CALLS['bwd'] += 1
+    ext.attention_key_mask_bwd(q, k, v, do_c, lse, delta, valid, dq, dk, dv, scale)
+
+
+class _KeyMaskAttnFn(torch.autograd.Function):
+    """Key-padding attention on q, k, v; `valid` is uint8 [B,Nk], no gradient."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, valid, scale):
+        ext = _load_extension()
+        KEY_MASK_CALLS['fwd'] += 1
+        o, lse = ext.attention_key_mask_fwd(q, k, v, valid, scale)
+        ctx.save_for_backward(q, k, v, o, lse, valid)
+        ctx.scale = scale
+        return o
+
+    @staticmethod
+    def backward(ctx, do):
+        q, k, v, o, lse, valid = ctx.saved_tensors
+        dq = torch.empty_like(q, memory_format=torch.contiguous_format)
+        dk = torch.empty_like(k, memory_format=torch.contiguous_format)
+        dv = torch.empty_like(v, memory_format=torch.contiguous_format)
+        _key_mask_backward(
+            _load_extension(), q, k, v, o, lse, do, valid, ctx.scale, dq, dk, dv)
+        return dq, dk, dv, None, None
+
+
+class _KeyMaskAttnQkvFn(torch.autograd.Function):
+    """Key-padding attention on packed [B,N,3,H,D] qkv, grads into one dqkv."""
+
+    @staticmethod
+    def forward(ctx, qkv, valid, scale):
+        ext = _load_extension()
+        q, k, v = (qkv[:, :, i].permute(0, 2, 1, 3) for i in range(3))
+        KEY_MASK_CALLS['fwd'] += 1
+        o, lse = ext.attention_key_mask_fwd(q, k, v, valid, scale)
+        ctx.save_for_backward(qkv, o, lse, valid)
+        ctx.scale = scale
+        return o
+
+    @staticmethod
+    def backward(ctx, do):
+        qkv, o, lse, valid = ctx.saved_tensors
+        q, k, v = (qkv[:, :, i].permute(0, 2, 1, 3) for i in range(3))
+        dqkv = torch.empty_like(qkv)
+        dq, dk, dv = (dqkv[:, :, i].permute(0, 2, 1, 3) for i in range(3))
+        _key_mask_backward(
+            _load_extension(), q, k, v, o, lse, do, valid, ctx.scale, dq, dk, dv)
+        return dqkv, None, None
+
+
 def flash_attention(
         q: torch.Tensor,
         k: torch.Tensor,
@@ -360,13 +479,22 @@ def flash_attention(
         dropout_p: float = 0.,
         scale: Optional[float] = None,
 ) -> torch.Tensor:
-    """Fused attention. q,k,v: [B, H, N, D]. attn_mask: additive, broadcastable to [B,H,Nq,Nk]."""
+    """Fused attention. q,k,v: [B, H, N, D]. attn_mask, broadcastable to
+    [B,H,Nq,Nk]: a float mask is added to the scores; a bool mask marks the
+    keys that take part (True), as in F.scaled_dot_product_attention, and a
+    query row with none gives zeros.  A bool [B,1,1,Nk] mask is a key-padding
+    mask and runs the key-mask kernels (rule next to _KEY_MASK_MIN_NK)."""
     if scale is None:
         scale = 1.0 / math.sqrt(q.shape[-1])
     if dropout_p > 0.:
         # attention-dropout path falls back to composition (rare in configs we target)
         return _dropout_sdpa(q, k, v, attn_mask, dropout_p, scale)
     if attention_available(q):
+        if attn_mask is not None and attn_mask.dtype == torch.bool:
+            valid = _key_valid(attn_mask, q, k, v)
+            if valid is not None:
+                return _KeyMaskAttnFn.apply(q, k, v, valid, scale)
+            attn_mask = _bool_to_additive(attn_mask)
         if attn_mask is not None:
             attn_mask = _prep_mask(attn_mask, q, k)
         return _FlashAttnFn.apply(q, k, v, attn_mask, scale)
@@ -388,7 +516,9 @@ def flash_attention_qkv(
 
     qkv: [B, N, 3, H, D] (the reshaped nn.Linear output — no permute/unbind
     copies).  Returns O as a [B,H,N,D] view of BNHD storage, so the usual
-    `transpose(1,2).reshape(B,N,C)` is free.
+    `transpose(1,2).reshape(B,N,C)` is free.  attn_mask as in
+    `flash_attention`: float = additive, bool = True takes part, bool
+    [B,1,1,N] = key-padding mask on the key-mask kernels.
     """
     B, N, three, H, D = qkv.shape
     assert three == 3
@@ -398,6 +528,11 @@ def flash_attention_qkv(
     if dropout_p == 0. and attention_available(q) and qkv.stride(-1) == 1:
         if attn_mask is not None:
             k = qkv[:, :, 1].permute(0, 2, 1, 3)
+            if attn_mask.dtype == torch.bool:
+                valid = _key_valid(attn_mask, q, k, qkv[:, :, 2].permute(0, 2, 1, 3))
+                if valid is not None:
+                    return _KeyMaskAttnQkvFn.apply(qkv, valid, scale)
+                attn_mask = _bool_to_additive(attn_mask)
             attn_mask = _prep_mask(attn_mask, q, k)
         return _FlashAttnQkvFn.apply(qkv, attn_mask, scale)
     k = qkv[:, :, 1].permute(0, 2, 1, 3)
@@ -407,8 +542,6 @@ def flash_attention_qkv(
 
 def _dropout_sdpa(q, k, v, attn_mask, dropout_p, scale):
     attn = (q @ k.transpose(-2, -1)) * scale
-    if attn_mask is not None:
-        attn = attn + _cyclic_mask(attn_mask, q.shape[0])
-    attn = attn.softmax(dim=-1)
+    attn = _masked_softmax(attn, attn_mask, q.shape[0])
     attn = F.dropout(attn, p=dropout_p, training=True)
     return attn @ v

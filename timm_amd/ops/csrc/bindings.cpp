@@ -45,6 +45,14 @@ void attention_bwd_single_pass(at::Tensor q, at::Tensor k, at::Tensor v,
                                at::Tensor dq, at::Tensor dk, at::Tensor dv,
                                double scale);
 
+// attention_key_mask.hip
+std::vector<at::Tensor> attention_key_mask_fwd(at::Tensor q, at::Tensor k, at::Tensor v,
+                                               at::Tensor valid, double scale);
+void attention_key_mask_bwd(at::Tensor q, at::Tensor k, at::Tensor v,
+                            at::Tensor dov, at::Tensor lse, at::Tensor delta,
+                            at::Tensor valid,
+                            at::Tensor dq, at::Tensor dk, at::Tensor dv, double scale);
+
 // window_attention.hip
 std::vector<at::Tensor> window_attention_fwd(
     at::Tensor qkv, c10::optional<at::Tensor> bias, int64_t heads,
@@ -117,6 +125,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("delta"), py::arg("mask"), py::arg("scale"), py::arg("nsplit") = 1);
   m.def("attention_bwd_single_pass", &attention_bwd_single_pass,
         "single-pass fused attention bwd, Nk <= 256, head_dim 64 (MFMA, gfx950)");
+  m.def("attention_key_mask_fwd", &attention_key_mask_fwd,
+        "key-padding attention fwd: uint8 [B,Nk] validity, head_dim 64 (MFMA, gfx950)");
+  m.def("attention_key_mask_bwd", &attention_key_mask_bwd,
+        "key-padding attention bwd: dQ and dK/dV passes, head_dim 64 (MFMA, gfx950)");
   m.def("window_attention_fwd", &window_attention_fwd,
         "windowed attention fwd on the feature map, head_dim 32, N <= 64 (MFMA, gfx950)");
   m.def("window_attention_bwd", &window_attention_bwd,
