@@ -6,10 +6,13 @@ log-spaced continuous relative position bias MLP (log-CPB, :98-201),
 post-norm residual blocks (:291), `PatchMerging` with post-reduction norm
 (:534), `SwinTransformerV2` (:719) and the window8/12/16/24 model grid.
 
-MI355X path: cosine attention folds the per-head logit scale into the
-normalized q, so the fused gfx950 flash kernel runs with scale=1 and the
-log-CPB bias (+ cyclic shift mask) as its additive `[num_win, nH, N, N]`
-mask — same fused route as our Swin V1.
+MI355X path: blocks with head_dim 32, window area <= 256 and no padding run
+`ops.window_attention(..., logit_scale=...)` on the un-partitioned map (cosine
+kernels of csrc/window_cos_attention.hip: shift, partition, normalisation and
+the shift mask inside the kernels).  Everything else folds the per-head logit
+scale into the normalized q, so the fused gfx950 flash kernel runs with
+scale=1 and the log-CPB bias (+ cyclic shift mask) as its additive
+`[num_win, nH, N, N]` mask.
 """
 import math
 from typing import Callable, Dict, List, Optional, Set, Tuple, Type, Union
@@ -19,7 +22,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ..data.constants import IMAGENET_DEFAULT_MEAN, IMAGENET_DEFAULT_STD
-from ..ops import flash_attention
+from ..ops import flash_attention, window_attention
 from ..ops.attention import attention_available
 from ..layers import ClassifierHead, DropPath, Mlp, PatchEmbed, get_act_layer, to_2tuple, to_ntuple, trunc_normal_
 from ._builder import build_model_with_cfg
@@ -292,8 +295,38 @@ class SwinTransformerV2Block(nn.Module):
             persistent=False,
         )
 
+    def _map_attn_ok(self, x) -> bool:
+        """Whether the cosine windowed-attention kernels can read this map in place."""
+        attn = self.attn
+        H, W = x.shape[1], x.shape[2]
+        if not (attn.attn_drop.p == 0. and self.dim == attn.num_heads * 32
+                and self.window_area <= 256
+                and H % self.window_size[0] == 0 and W % self.window_size[1] == 0):
+            return False
+        return x.dtype == torch.bfloat16 and attention_available(
+            x.new_empty((1, attn.num_heads, 1, 32)))
+
     def _attn(self, x: torch.Tensor) -> torch.Tensor:
         B, H, W, C = x.shape
+
+        if self._map_attn_ok(x):
+            # shift, partition, reverse, the shift mask and the q / k
+            # normalisation happen inside the kernels: qkv runs on the map
+            attn = self.attn
+            if attn.q_bias is None:
+                qkv = attn.qkv(x)
+            else:
+                qkv_bias = torch.cat((attn.q_bias, attn.k_bias, attn.v_bias))
+                if attn.qkv_bias_separate:
+                    qkv = attn.qkv(x)
+                    qkv += qkv_bias
+                else:
+                    qkv = F.linear(x, weight=attn.qkv.weight, bias=qkv_bias)
+            logit_scale = torch.clamp(attn.logit_scale, max=math.log(1. / 0.01)).exp()
+            x = window_attention(
+                qkv, attn.num_heads, self.window_size, self.shift_size,
+                bias=attn._get_rel_pos_bias()[0], logit_scale=logit_scale)
+            return attn.proj_drop(attn.proj(x))
 
         # cyclic shift
         has_shift = any(self.shift_size)

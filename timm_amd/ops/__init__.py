@@ -14,6 +14,8 @@ hand-written CDNA4 (gfx950) HIP kernel compiled into the in-tree extension
    mean "True takes part" on every attention path
  * window_attention (Swin W-MSA / SW-MSA on the map)   — shift, partition, reverse and shift mask
    as addressing; one wave per (window, head), single-pass bwd with dBias (head_dim 32, N <= 64)
+ * window_attention(..., logit_scale=) (SwinV2 cosine) — q / k normalised in the kernels, fp32 logit
+   scale, one workgroup per (window, head), bwd with d logit_scale and dBias (head_dim 32, N <= 256)
  * bias_act (bias+GELU/SiLU epilogue after GEMM)
  * residual add (+ LayerScale + DropPath) epilogue
  * multi-tensor fused optimizer steps (AdamW/LAMB/SGD/lerp-EMA)

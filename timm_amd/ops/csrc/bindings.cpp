@@ -63,6 +63,15 @@ std::tuple<at::Tensor, c10::optional<at::Tensor>> window_attention_bwd(
     int64_t wh, int64_t ww, int64_t sh, int64_t sw, double scale,
     bool need_dbias, int64_t nsplit);
 
+// window_cos_attention.hip
+std::vector<at::Tensor> window_cos_attention_fwd(
+    at::Tensor qkv, c10::optional<at::Tensor> bias, at::Tensor logit_scale, int64_t heads,
+    int64_t wh, int64_t ww, int64_t sh, int64_t sw);
+std::tuple<at::Tensor, at::Tensor, c10::optional<at::Tensor>> window_cos_attention_bwd(
+    at::Tensor qkv, at::Tensor o, at::Tensor lse, at::Tensor dout,
+    c10::optional<at::Tensor> bias, at::Tensor logit_scale, int64_t heads,
+    int64_t wh, int64_t ww, int64_t sh, int64_t sw, bool need_dbias, int64_t nsplit);
+
 // depthwise_conv.hip
 at::Tensor dwconv_fwd(at::Tensor x, at::Tensor w_t, c10::optional<at::Tensor> bias,
                       long stride, long pad, long K, long Ho, long Wo);
@@ -133,6 +142,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "windowed attention fwd on the feature map, head_dim 32, N <= 64 (MFMA, gfx950)");
   m.def("window_attention_bwd", &window_attention_bwd,
         "windowed attention bwd on the feature map: dqkv and dbias in one pass (MFMA, gfx950)");
+  m.def("window_cos_attention_fwd", &window_cos_attention_fwd,
+        "cosine (SwinV2) windowed attention fwd on the feature map, head_dim 32, N <= 256 (MFMA, gfx950)");
+  m.def("window_cos_attention_bwd", &window_cos_attention_bwd,
+        "cosine windowed attention bwd: dqkv, d logit_scale partials, dbias (MFMA, gfx950)");
   m.def("dwconv_fwd", &dwconv_fwd, "NHWC depthwise conv fwd (gfx950)");
   m.def("dwconv_bwd_data", &dwconv_bwd_data, "NHWC depthwise conv bwd-data");
   m.def("dwconv_bwd_weight", &dwconv_bwd_weight, "NHWC depthwise conv bwd-weight");

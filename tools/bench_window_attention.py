@@ -37,6 +37,9 @@ def parse_args():
     p.add_argument('--batch', type=int, default=128)
     p.add_argument('--window', type=int, default=7)
     p.add_argument('--shift', action='store_true', help='SW-MSA block (shift = window // 2)')
+    p.add_argument('--cosine', action='store_true',
+                   help='SwinV2 block (cosine attention, log-CPB bias); see cosine_fwd()')
+    p.add_argument('--img', type=int, default=256, help='--cosine: image side, map = img / 4 / 2^(stage-1)')
     p.add_argument('--warmup', type=int, default=10)
     p.add_argument('--iters', type=int, default=30)
     return p.parse_args()
@@ -53,16 +56,32 @@ def main():
 
     side, heads = STAGES[args.stage]
     B, win, dim = args.batch, args.window, heads * 32
+    if args.cosine:  # SwinV2-B stage shapes, window clamped to the map
+        from timm_amd.models.swin_transformer_v2 import SwinTransformerV2Block
+        side = args.img // 4 >> (args.stage - 1)
+        win = min(win, side)
     shift = win // 2 if args.shift and side > win else 0
     dev = torch.device('cuda:0')
     torch.manual_seed(0)
-    blk = SwinTransformerBlock(dim, (side, side), num_heads=heads, window_size=win,
-                               shift_size=shift).to(dev, torch.bfloat16)
+    blk = (SwinTransformerV2Block if args.cosine else SwinTransformerBlock)(
+        dim, (side, side), num_heads=heads, window_size=win, shift_size=shift).to(dev, torch.bfloat16)
     attn = blk.attn
     x = torch.randn(B, side, side, dim, device=dev, dtype=torch.bfloat16, requires_grad=True)
     do = torch.randn(B, side, side, dim, device=dev, dtype=torch.bfloat16)
 
-    if args.impl == 'map':
+    if args.cosine:
+        # Both arms time the block's own `_attn` (qkv Linear + attention +
+        # proj, map in and map out): `map` takes the cosine kernels,
+        # `partition` is the same block with the gate shut, i.e. roll /
+        # partition / normalize / flash_attention / reverse.
+        if args.impl == 'partition':
+            blk._map_attn_ok = lambda x: False
+        inputs = (x, attn.qkv.weight, attn.q_bias, attn.v_bias, attn.logit_scale,
+                  attn.cpb_mlp[0].weight, attn.proj.weight)
+
+        def fwd():
+            return blk._attn(x)
+    elif args.impl == 'map':
         def fwd():
             return ops.window_attention(attn.qkv(x), heads, win, shift,
                                         bias=attn._get_rel_pos_bias()[0], scale=attn.scale)
@@ -80,7 +99,8 @@ def main():
             o = window_reverse(o, (win, win), side, side)
             return torch.roll(o, (shift, shift), (1, 2)) if shift else o
 
-    inputs = (x, attn.qkv.weight, attn.qkv.bias, attn.relative_position_bias_table)
+    if not args.cosine:
+        inputs = (x, attn.qkv.weight, attn.qkv.bias, attn.relative_position_bias_table)
 
     def step():
         return torch.autograd.grad(fwd(), inputs, do)
@@ -100,9 +120,10 @@ def main():
     times.sort()
     q1, _, q3 = statistics.quantiles(times, n=4)
     print(json.dumps({
-        'impl': args.impl, 'stage': args.stage, 'shift': shift,
+        'impl': args.impl, 'cosine': args.cosine, 'stage': args.stage, 'shift': shift,
         'shape': {'B': B, 'map': side, 'heads': heads, 'window': win, 'D': 32},
-        'what': 'qkv Linear + window attention, forward+backward, device events',
+        'what': ('SwinV2 block _attn (qkv Linear + cosine window attention + proj)' if args.cosine
+                 else 'qkv Linear + window attention') + ', forward+backward, device events',
         'iters': args.iters, 'warmup': args.warmup,
         'median_us': round(statistics.median(times), 1), 'min_us': round(times[0], 1),
         'max_us': round(times[-1], 1), 'q1_us': round(q1, 1), 'q3_us': round(q3, 1),
