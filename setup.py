@@ -24,6 +24,7 @@ sources = [
     os.path.join(CSRC, 'attention_key_mask.hip'),
     os.path.join(CSRC, 'window_attention.hip'),
     os.path.join(CSRC, 'window_cos_attention.hip'),
+    os.path.join(CSRC, 'xca_attention.hip'),
     os.path.join(CSRC, 'depthwise_conv.hip'),
     os.path.join(CSRC, 'multi_tensor.hip'),
     os.path.join(CSRC, 'muon_ns.hip'),

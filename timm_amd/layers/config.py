@@ -13,7 +13,7 @@ from typing import Any, Optional
 __all__ = [
     'is_no_jit', 'set_no_jit', 'is_exportable', 'set_exportable', 'is_scriptable', 'set_scriptable',
     'set_layer_config', 'use_fused_attn', 'set_fused_attn', 'use_reentrant_ckpt', 'set_reentrant_ckpt',
-    'use_fused_rope', 'set_fused_rope',
+    'use_fused_rope', 'set_fused_rope', 'use_fused_xca', 'set_fused_xca',
 ]
 
 # module-level state
@@ -26,6 +26,9 @@ _USE_FUSED_ATTN = int(os.environ.get('TIMM_AMD_FUSED_ATTN', os.environ.get('TIMM
 
 # None == follow TIMM_AMD_FUSED_ROPE (read at call time, default on)
 _USE_FUSED_ROPE: Optional[bool] = None
+
+# None == follow TIMM_AMD_FUSED_XCA (read at call time, default on)
+_USE_FUSED_XCA: Optional[bool] = None
 
 _USE_REENTRANT_CKPT = False
 
@@ -85,6 +88,22 @@ def set_fused_rope(enable: Optional[bool] = True):
     """True/False overrides TIMM_AMD_FUSED_ROPE; None follows it again."""
     global _USE_FUSED_ROPE
     _USE_FUSED_ROPE = None if enable is None else bool(enable)
+
+
+def use_fused_xca() -> bool:
+    """Gates the cross-covariance attention kernels behind
+    `ops.cross_covariance_attention` (XCiT's XCA).  Checked on every forward."""
+    if _EXPORTABLE or _SCRIPTABLE or _NO_JIT:
+        return False
+    if _USE_FUSED_XCA is not None:
+        return _USE_FUSED_XCA
+    return int(os.environ.get('TIMM_AMD_FUSED_XCA', '1')) > 0
+
+
+def set_fused_xca(enable: Optional[bool] = True):
+    """True/False overrides TIMM_AMD_FUSED_XCA; None follows it again."""
+    global _USE_FUSED_XCA
+    _USE_FUSED_XCA = None if enable is None else bool(enable)
 
 
 def use_reentrant_ckpt() -> bool:

@@ -16,6 +16,9 @@ hand-written CDNA4 (gfx950) HIP kernel compiled into the in-tree extension
    as addressing; one wave per (window, head), single-pass bwd with dBias (head_dim 32, N <= 64)
  * window_attention(..., logit_scale=) (SwinV2 cosine) — q / k normalised in the kernels, fp32 logit
    scale, one workgroup per (window, head), bwd with d logit_scale and dBias (head_dim 32, N <= 256)
+ * cross_covariance_attention (XCiT's XCA)              — softmax over the d x d channel matrix of
+   token-normalised q, k on the packed qkv; one workgroup per (batch, head), two passes over the
+   tokens, closed-form bwd with d temperature (head_dim 32 / 48 / 64, any N)
  * bias_act (bias+GELU/SiLU epilogue after GEMM)
  * residual add (+ LayerScale + DropPath) epilogue
  * multi-tensor fused optimizer steps (AdamW/LAMB/SGD/lerp-EMA)
@@ -81,6 +84,7 @@ from .conv import depthwise_conv2d  # noqa: E402
 from .layer_norm import layer_norm_act, rms_norm_act, layer_norm, rms_norm  # noqa: E402
 from .attention import flash_attention, flash_attention_qkv, attention_available  # noqa: E402
 from .window_attention import window_attention  # noqa: E402
+from .xca_attention import cross_covariance_attention  # noqa: E402
 from .elementwise import bias_act, residual_scale_add  # noqa: E402
 from .fused_optim import fused_adamw_step, fused_lamb_step, fused_lerp_, fused_l2norm  # noqa: E402
 from .loss import fused_cross_entropy  # noqa: E402
@@ -92,6 +96,7 @@ __all__ = [
     'depthwise_conv2d',
     'layer_norm', 'layer_norm_act', 'rms_norm', 'rms_norm_act',
     'flash_attention', 'flash_attention_qkv', 'attention_available', 'window_attention',
+    'cross_covariance_attention',
     'bias_act', 'residual_scale_add',
     'fused_adamw_step', 'fused_lamb_step', 'fused_lerp_', 'fused_l2norm',
     'fused_cross_entropy', 'u8_normalize', 'masked_global_pool',

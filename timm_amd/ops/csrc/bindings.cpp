@@ -63,6 +63,12 @@ std::tuple<at::Tensor, c10::optional<at::Tensor>> window_attention_bwd(
     int64_t wh, int64_t ww, int64_t sh, int64_t sw, double scale,
     bool need_dbias, int64_t nsplit);
 
+// xca_attention.hip
+std::vector<at::Tensor> xca_attention_fwd(at::Tensor qkv, at::Tensor temperature, int64_t heads);
+std::vector<at::Tensor> xca_attention_bwd(
+    at::Tensor qkv, at::Tensor dout, at::Tensor temperature, at::Tensor c, at::Tensor inv,
+    int64_t heads);
+
 // window_cos_attention.hip
 std::vector<at::Tensor> window_cos_attention_fwd(
     at::Tensor qkv, c10::optional<at::Tensor> bias, at::Tensor logit_scale, int64_t heads,
@@ -146,6 +152,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "cosine (SwinV2) windowed attention fwd on the feature map, head_dim 32, N <= 256 (MFMA, gfx950)");
   m.def("window_cos_attention_bwd", &window_cos_attention_bwd,
         "cosine windowed attention bwd: dqkv, d logit_scale partials, dbias (MFMA, gfx950)");
+  m.def("xca_attention_fwd", &xca_attention_fwd,
+        "cross-covariance attention (XCiT) fwd on the packed qkv, head_dim 32/48/64 (MFMA, gfx950)");
+  m.def("xca_attention_bwd", &xca_attention_bwd,
+        "cross-covariance attention bwd: dqkv and d temperature partials (MFMA, gfx950)");
   m.def("dwconv_fwd", &dwconv_fwd, "NHWC depthwise conv fwd (gfx950)");
   m.def("dwconv_bwd_data", &dwconv_bwd_data, "NHWC depthwise conv bwd-data");
   m.def("dwconv_bwd_weight", &dwconv_bwd_weight, "NHWC depthwise conv bwd-weight");
