@@ -22,6 +22,7 @@ sources = [
     os.path.join(CSRC, 'attention_bwd_single_pass.hip'),
     os.path.join(CSRC, 'attention_head_dims.hip'),
     os.path.join(CSRC, 'attention_key_mask.hip'),
+    os.path.join(CSRC, 'attention_rel_pos.hip'),
     os.path.join(CSRC, 'window_attention.hip'),
     os.path.join(CSRC, 'window_cos_attention.hip'),
     os.path.join(CSRC, 'xca_attention.hip'),

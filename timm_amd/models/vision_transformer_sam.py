@@ -16,8 +16,10 @@ from ..data.constants import IMAGENET_DEFAULT_MEAN, IMAGENET_DEFAULT_STD, IMAGEN
 from ..layers import (
     ClassifierHead, DropPath, LayerNorm2d, LayerScale, Mlp, NormMlpClassifierHead, PatchDropout,
     PatchEmbed, RotaryEmbeddingCat, apply_rot_embed_cat, resample_abs_pos_embed_nhwc, to_2tuple,
+    use_fused_attn,
 )
 from ..layers.format import Format
+from .. import ops
 from ._builder import build_model_with_cfg
 from ._features import feature_take_indices
 from ._manipulate import checkpoint, checkpoint_seq
@@ -45,6 +47,26 @@ def get_rel_pos(q_size: int, k_size: int, rel_pos: torch.Tensor) -> torch.Tensor
     return rel_pos_resized[relative_coords.long()]
 
 
+def get_decomposed_rel_pos_tables(
+        q: torch.Tensor,
+        rel_pos_h: torch.Tensor,
+        rel_pos_w: torch.Tensor,
+        q_size: Tuple[int, int],
+        k_size: Tuple[int, int],
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The two tables of the decomposed relative position bias for q
+    [..., q_h * q_w, dim]: rel_h [..., q_h, q_w, k_h] and rel_w [..., q_h, q_w, k_w]."""
+    q_h, q_w = q_size
+    k_h, k_w = k_size
+    Rh = get_rel_pos(q_h, k_h, rel_pos_h)
+    Rw = get_rel_pos(q_w, k_w, rel_pos_w)
+
+    r_q = q.reshape(q.shape[:-2] + (q_h, q_w, q.shape[-1]))
+    rel_h = torch.einsum('...hwc,hkc->...hwk', r_q, Rh)
+    rel_w = torch.einsum('...hwc,wkc->...hwk', r_q, Rw)
+    return rel_h, rel_w
+
+
 def get_decomposed_rel_pos_bias(
         q: torch.Tensor,
         rel_pos_h: torch.Tensor,
@@ -55,13 +77,7 @@ def get_decomposed_rel_pos_bias(
     """Decomposed (axis-separable) relative position bias from MViT-V2."""
     q_h, q_w = q_size
     k_h, k_w = k_size
-    Rh = get_rel_pos(q_h, k_h, rel_pos_h)
-    Rw = get_rel_pos(q_w, k_w, rel_pos_w)
-
-    B, _, dim = q.shape
-    r_q = q.reshape(B, q_h, q_w, dim)
-    rel_h = torch.einsum('bhwc,hkc->bhwk', r_q, Rh)
-    rel_w = torch.einsum('bhwc,wkc->bhwk', r_q, Rw)
+    rel_h, rel_w = get_decomposed_rel_pos_tables(q, rel_pos_h, rel_pos_w, q_size, k_size)
     attn_bias = rel_h[:, :, :, :, None] + rel_w[:, :, :, None, :]
     return attn_bias.reshape(-1, q_h * q_w, k_h * k_w)
 
@@ -93,28 +109,50 @@ class Attention(nn.Module):
         B, H, W, _ = x.shape
         N = H * W
         x = x.reshape(B, N, -1)
-        qkv = self.qkv(x).view(B, N, 3, self.num_heads, -1).permute(2, 0, 3, 1, 4)
-        q, k, v = qkv.reshape(3, B * self.num_heads, N, -1).unbind(0)
-        q, k = self.q_norm(q), self.k_norm(k)
-
-        if self.use_rel_pos:
-            attn_bias = get_decomposed_rel_pos_bias(q, self.rel_pos_h, self.rel_pos_w, (H, W), (H, W))
+        if use_fused_attn() and x.is_cuda:
+            x = self._fused_attention(x, H, W)
         else:
-            attn_bias = None
-            if self.rope is not None:
-                rope = self.rope.get_embed()
-                q = apply_rot_embed_cat(q, rope).type_as(v)
-                k = apply_rot_embed_cat(k, rope).type_as(v)
+            qkv = self.qkv(x).view(B, N, 3, self.num_heads, -1).permute(2, 0, 3, 1, 4)
+            q, k, v = qkv.reshape(3, B * self.num_heads, N, -1).unbind(0)
+            q, k = self.q_norm(q), self.k_norm(k)
 
-        x = torch.nn.functional.scaled_dot_product_attention(
-            q, k, v, attn_mask=attn_bias,
-            dropout_p=self.attn_drop.p if self.training else 0.)
+            if self.use_rel_pos:
+                attn_bias = get_decomposed_rel_pos_bias(q, self.rel_pos_h, self.rel_pos_w, (H, W), (H, W))
+            else:
+                attn_bias = None
+                if self.rope is not None:
+                    rope = self.rope.get_embed()
+                    q = apply_rot_embed_cat(q, rope).type_as(v)
+                    k = apply_rot_embed_cat(k, rope).type_as(v)
 
-        x = x.view(B, self.num_heads, N, -1).transpose(1, 2).reshape(B, N, -1)
+            x = torch.nn.functional.scaled_dot_product_attention(
+                q, k, v, attn_mask=attn_bias,
+                dropout_p=self.attn_drop.p if self.training else 0.)
+
+            x = x.view(B, self.num_heads, N, -1).transpose(1, 2).reshape(B, N, -1)
         x = self.proj(x)
         x = self.proj_drop(x)
         x = x.view(B, H, W, -1)
         return x
+
+    def _fused_attention(self, x, H: int, W: int):
+        """HIP attention on [B,H,N,d] views of the qkv output; the rel-pos
+        bias goes in as its two tables, never as a [B*heads, N, N] tensor."""
+        B, N, _ = x.shape
+        qkv = self.qkv(x).view(B, N, 3, self.num_heads, -1)
+        q, k, v = [qkv[:, :, i].permute(0, 2, 1, 3) for i in range(3)]
+        q, k = self.q_norm(q), self.k_norm(k)
+        rel_pos_hw = None
+        if self.use_rel_pos:
+            rel_h, rel_w = get_decomposed_rel_pos_tables(q, self.rel_pos_h, self.rel_pos_w, (H, W), (H, W))
+            rel_pos_hw = (rel_h.reshape(B, self.num_heads, N, H), rel_w.reshape(B, self.num_heads, N, W))
+        elif self.rope is not None:
+            rope = self.rope.get_embed()
+            q = apply_rot_embed_cat(q, rope).type_as(v)
+            k = apply_rot_embed_cat(k, rope).type_as(v)
+        x = ops.flash_attention(
+            q, k, v, dropout_p=self.attn_drop.p if self.training else 0., rel_pos_hw=rel_pos_hw)
+        return x.transpose(1, 2).reshape(B, N, -1)
 
 
 class Block(nn.Module):

@@ -12,6 +12,8 @@ hand-written CDNA4 (gfx950) HIP kernel compiled into the in-tree extension
  * key-padding attention (bool [B,1,1,Nk] attn_mask)   — validity as bits in scalar registers,
    all-padding key tiles skipped before their loads, fwd + bwd (head_dim 64); bool masks
    mean "True takes part" on every attention path
+ * decomposed rel-pos attention (rel_pos_hw= tables)   — SAM / MViT-v2 bias from its [B,H,N,Kh] and
+   [B,H,N,Kw] tables in LDS, table gradients as row sums of dS in the dQ kernel (head_dim 64)
  * window_attention (Swin W-MSA / SW-MSA on the map)   — shift, partition, reverse and shift mask
    as addressing; one wave per (window, head), single-pass bwd with dBias (head_dim 32, N <= 64)
  * window_attention(..., logit_scale=) (SwinV2 cosine) — q / k normalised in the kernels, fp32 logit

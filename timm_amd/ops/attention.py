@@ -53,6 +53,17 @@ directions are hand-written flash-style gfx950 HIP kernels:
    fp32 tensor is built or read.  KEY_MASK_CALLS counts their calls.  Every
    other bool mask (other shapes, head dims, dtypes, Nk > 4096) becomes the
    additive fp32 mask (finfo.min at False) of the kernels above.
+ * decomposed rel-pos bias (MViT-v2 / SAM): `rel_pos_hw=(rel_h, rel_w)` with
+   rel_h [B,H,Nq,Kh], rel_w [B,H,Nq,Kw] and Nk = Kh * Kw adds
+   rel_h[q, j // Kw] + rel_w[q, j % Kw] to score (q, j); the tables are not
+   scaled.  At bf16, head_dim 64, Kh, Kw <= 64 and no mask it runs the
+   kernels of csrc/attention_rel_pos.hip, which keep the Kh + Kw values of a
+   query row in LDS and return the table gradients as row sums of dS from
+   the dQ kernel - no [B,H,Nq,Nk] bias or bias gradient is built.
+   REL_POS_CALLS counts their calls.  Every other call (CPU, other head dims
+   or dtypes, larger grids, a mask as well, dropout, TIMM_AMD_ATTN_BWD=gemm)
+   sums the tables to a float [B,H,Nq,Nk] mask for the paths above, and
+   autograd reduces its gradient back to the tables.
  * flash_attention_qkv: packed-qkv entry — takes the [B,N,3,H,D] projection
    output directly and writes gradients into one packed dqkv buffer, so the
    qkv-unbind `aten::copy_`/stack grad chain never appears in the graph.
@@ -62,7 +73,7 @@ numerics oracle for the GPU tests.
 """
 import math
 import os
-from typing import Optional
+from typing import Optional, Tuple
 
 import torch
 import torch.nn.functional as F
@@ -214,6 +225,16 @@ _KEY_MASK_MIN_NK = 1
 _KEY_MASK_MAX_NK = 4096
 # calls of the key-mask kernels since import: lets a test assert that they ran
 KEY_MASK_CALLS = {'fwd': 0, 'bwd': 0}
+# Decomposed rel-pos tables (rel_pos_hw=) run the kernels of
+# csrc/attention_rel_pos.hip when q/k/v are bf16 with head_dim 64 and aligned
+# rows, Kh, Kw <= _REL_POS_MAX_K (the tables of a 64-query tile live in LDS),
+# both tables share one dtype (bf16 or fp32), and there is no mask, no dropout
+# and TIMM_AMD_ATTN_BWD is not 'gemm'.  They are a two-pass pair behind
+# attn_bwd_preprocess for every Nk; set_attn_bwd_path does not apply to them.
+# Numbers: profiles/attn_rel_pos/README.md.
+_REL_POS_MAX_K = 64
+# calls of the rel-pos kernels since import: lets a test assert that they ran
+REL_POS_CALLS = {'fwd': 0, 'bwd': 0}
 _BWD_PATHS = ('two_pass', 'single_pass', 'single_pass_preprocess')
 _BWD_PATH_FORCED: Optional[str] = None
 # calls per path since import: lets a test assert which kernels ran
@@ -447,6 +468,66 @@ class _KeyMaskAttnFn(torch.autograd.Function):
         return dq, dk, dv, None, None
 
 
+def _rel_pos_kernels_ok(q, k, v, rel_h, rel_w):
+    """Whether the rel-pos kernels serve this call (q already known to be on
+    the GPU in bf16 with the extension loaded); rule next to _REL_POS_MAX_K."""
+    B, H, Nq = q.shape[:3]
+    Kh, Kw = rel_h.shape[-1], rel_w.shape[-1]
+    return (_BWD_MODE != 'gemm' and q.numel() > 0 and B * H <= 65535
+            and all(t.shape[-1] == 64 and _aligned16(t) for t in (q, k, v))
+            and 1 <= Kh <= _REL_POS_MAX_K and 1 <= Kw <= _REL_POS_MAX_K
+            and rel_h.is_cuda and rel_w.is_cuda
+            and rel_h.dtype == rel_w.dtype and rel_h.dtype in (torch.bfloat16, torch.float32)
+            and tuple(rel_h.shape) == (B, H, Nq, Kh) and tuple(rel_w.shape) == (B, H, Nq, Kw))
+
+
+class _RelPosAttnFn(torch.autograd.Function):
+    """Attention with the decomposed rel-pos tables rel_h [B,H,Nq,Kh] and
+    rel_w [B,H,Nq,Kw]; their gradients come from the dQ kernel."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, rel_h, rel_w, scale):
+        ext = _load_extension()
+        rel_h, rel_w = rel_h.contiguous(), rel_w.contiguous()
+        REL_POS_CALLS['fwd'] += 1
+        o, lse = ext.attention_rel_pos_fwd(q, k, v, rel_h, rel_w, scale)
+        ctx.save_for_backward(q, k, v, o, lse, rel_h, rel_w)
+        ctx.scale = scale
+        return o
+
+    @staticmethod
+    def backward(ctx, do):
+        q, k, v, o, lse, rel_h, rel_w = ctx.saved_tensors
+        ext = _load_extension()
+        dq = torch.empty_like(q, memory_format=torch.contiguous_format)
+        dk = torch.empty_like(k, memory_format=torch.contiguous_format)
+        dv = torch.empty_like(v, memory_format=torch.contiguous_format)
+        if _preprocess_ok(do):
+            do_c, delta = ext.attn_bwd_preprocess(do, o)
+        else:
+            do_c = do.contiguous()
+            delta = (do_c * o).float().sum(-1)
+        REL_POS_CALLS['bwd'] += 1
+        drel_h, drel_w = ext.attention_rel_pos_bwd(
+            q, k, v, do_c, lse, delta, rel_h, rel_w, dq, dk, dv, ctx.scale)
+        return dq, dk, dv, drel_h, drel_w, None
+
+
+def _rel_pos_as_mask(rel_pos_hw, attn_mask, q, k):
+    """The tables summed to a float [B,H,Nq,Nk] mask (plus `attn_mask`) for
+    the paths without the rel-pos kernels; autograd reduces the mask gradient
+    back to the tables."""
+    rel_h, rel_w = rel_pos_hw
+    B, H, Nq = q.shape[:3]
+    bias = rel_h.float()[..., :, None] + rel_w.float()[..., None, :]
+    bias = bias.reshape(B, H, Nq, k.shape[2])
+    if attn_mask is None:
+        return bias
+    if attn_mask.dtype == torch.bool:  # finfo.min itself, not finfo.min + bias
+        return bias.masked_fill(~attn_mask, torch.finfo(torch.float32).min)
+    return bias + attn_mask
+
+
 class _KeyMaskAttnQkvFn(torch.autograd.Function):
     """Key-padding attention on packed [B,N,3,H,D] qkv, grads into one dqkv."""
 
@@ -478,14 +559,27 @@ def flash_attention(
         attn_mask: Optional[torch.Tensor] = None,
         dropout_p: float = 0.,
         scale: Optional[float] = None,
+        rel_pos_hw: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
 ) -> torch.Tensor:
     """Fused attention. q,k,v: [B, H, N, D]. attn_mask, broadcastable to
     [B,H,Nq,Nk]: a float mask is added to the scores; a bool mask marks the
     keys that take part (True), as in F.scaled_dot_product_attention, and a
     query row with none gives zeros.  A bool [B,1,1,Nk] mask is a key-padding
-    mask and runs the key-mask kernels (rule next to _KEY_MASK_MIN_NK)."""
+    mask and runs the key-mask kernels (rule next to _KEY_MASK_MIN_NK).
+    rel_pos_hw = (rel_h [B,H,Nq,Kh], rel_w [B,H,Nq,Kw]) with Nk = Kh * Kw is
+    the decomposed rel-pos bias rel_h[q, j // Kw] + rel_w[q, j % Kw], added
+    unscaled; it runs the rel-pos kernels (rule next to _REL_POS_MAX_K)."""
     if scale is None:
         scale = 1.0 / math.sqrt(q.shape[-1])
+    if rel_pos_hw is not None:
+        rel_h, rel_w = rel_pos_hw
+        assert k.shape[2] == rel_h.shape[-1] * rel_w.shape[-1], 'Nk must equal Kh * Kw'
+        if (attn_mask is None and dropout_p == 0. and attention_available(q)
+                and _rel_pos_kernels_ok(q, k, v, rel_h, rel_w)):
+            return _RelPosAttnFn.apply(q, k, v, rel_h, rel_w, scale)
+        attn_mask = _rel_pos_as_mask(rel_pos_hw, attn_mask, q, k)
+        if dropout_p > 0.:  # that composition runs in q's dtype
+            attn_mask = attn_mask.to(q.dtype)
     if dropout_p > 0.:
         # attention-dropout path falls back to composition (rare in configs we target)
         return _dropout_sdpa(q, k, v, attn_mask, dropout_p, scale)

@@ -53,6 +53,15 @@ void attention_key_mask_bwd(at::Tensor q, at::Tensor k, at::Tensor v,
                             at::Tensor valid,
                             at::Tensor dq, at::Tensor dk, at::Tensor dv, double scale);
 
+// attention_rel_pos.hip
+std::vector<at::Tensor> attention_rel_pos_fwd(at::Tensor q, at::Tensor k, at::Tensor v,
+                                              at::Tensor rel_h, at::Tensor rel_w, double scale);
+std::vector<at::Tensor> attention_rel_pos_bwd(at::Tensor q, at::Tensor k, at::Tensor v,
+                                              at::Tensor dov, at::Tensor lse, at::Tensor delta,
+                                              at::Tensor rel_h, at::Tensor rel_w,
+                                              at::Tensor dq, at::Tensor dk, at::Tensor dv,
+                                              double scale);
+
 // window_attention.hip
 std::vector<at::Tensor> window_attention_fwd(
     at::Tensor qkv, c10::optional<at::Tensor> bias, int64_t heads,
@@ -144,6 +153,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "key-padding attention fwd: uint8 [B,Nk] validity, head_dim 64 (MFMA, gfx950)");
   m.def("attention_key_mask_bwd", &attention_key_mask_bwd,
         "key-padding attention bwd: dQ and dK/dV passes, head_dim 64 (MFMA, gfx950)");
+  m.def("attention_rel_pos_fwd", &attention_rel_pos_fwd,
+        "attention fwd with decomposed rel-pos tables [B,H,Nq,Kh] / [B,H,Nq,Kw], head_dim 64 (MFMA, gfx950)");
+  m.def("attention_rel_pos_bwd", &attention_rel_pos_bwd,
+        "decomposed rel-pos attention bwd: dQ + table gradients and dK/dV passes (MFMA, gfx950)");
   m.def("window_attention_fwd", &window_attention_fwd,
         "windowed attention fwd on the feature map, head_dim 32, N <= 64 (MFMA, gfx950)");
   m.def("window_attention_bwd", &window_attention_bwd,
